@@ -2,6 +2,13 @@
 """flyimg hot-path benchmark on MI355X (contract: see README / DESIGN.md).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+``--full`` adds everything else the line can carry: the oracle check of the
+last timed batch, the instrumented stage pass and the CPU baseline.
+``--dump-outputs DIR`` writes what the last timed step computed (result
+records and a seeded sample of the output pixels) as DIR/<name>.npy.
 
 Ranks: under torch.distributed.run (WORLD_SIZE set) each process is one rank
 and WORLD_SIZE must equal --gpus; without a launcher, --gpus N > 1 starts N
@@ -244,6 +251,64 @@ def launch_ranks(n: int) -> int:
 # batches in flight per context: the library's slots (fi_api.cpp kSlots)
 PIPE_DEPTH = 3
 
+# --dump-outputs: float32 bytes of sampled output pixels (with the float64
+# records of a 65536-image step, about 6 MB, the files stay under 64 MB)
+DUMP_PIXEL_BYTES = 48 << 20
+DUMP_RECORD_FIELDS = ("status", "out_w", "out_h", "out_channels", "crop_x", "crop_y", "crop_w", "crop_h",
+                      "crop_score", "n_candidates")
+
+
+def dump_outputs(ctx, out_dir, tag, arrs, image_ids, pix_arr, pix_base, seed=20250112):
+    """``--dump-outputs``: what a caller of the timed path holds after its last
+    step, as .npy files under ``out_dir``.
+
+    records<tag>.npy       float64 (n, 11): the global image index, then
+                           DUMP_RECORD_FIELDS of every image of the step
+                           (``arrs``: the step's descriptor arrays in order,
+                           ``image_ids``: their images' global indices)
+    pixels<tag>.npy        float32, flat: the output pixels (out_h x out_w x
+                           out_channels, row padding dropped) of a fixed seeded
+                           sample of the images of ``pix_arr``, the batch whose
+                           outputs are still in its dst buffers (the step's
+                           last), at most DUMP_PIXEL_BYTES
+    pixel_index<tag>.npy   float64 (m, 2): per sampled image its row in
+                           records and its offset into pixels
+    ``pix_base``: the row of pix_arr's first image in records."""
+    import numpy as np
+
+    from flyimg_amd import _lib as L
+
+    os.makedirs(out_dir, exist_ok=True)
+    cols = []
+    for a in arrs:
+        v = L.struct_view(a)
+        cols.append(np.stack([v[f].astype(np.float64) for f in DUMP_RECORD_FIELDS], axis=1))
+    rec = np.concatenate([np.asarray(image_ids, dtype=np.float64)[:, None], np.concatenate(cols)], axis=1)
+    np.save(os.path.join(out_dir, f"records{tag}.npy"), rec)
+    v = L.struct_view(pix_arr)
+    size = v["out_h"].astype(np.int64) * v["out_w"] * v["out_channels"]
+    size[v["status"] != 0] = 0
+    budget = DUMP_PIXEL_BYTES // 4
+    chosen = []
+    for i in np.random.default_rng(seed).permutation(len(size)):
+        if size[i] <= 0:
+            continue
+        if size[i] > budget:
+            break
+        budget -= int(size[i])
+        chosen.append(int(i))
+    chosen.sort()
+    pix, index, off = [], [], 0
+    for i in chosen:
+        a = pix_arr[i]
+        out = ctx.d2h(a.dst, a.out_h * a.out_stride).reshape(a.out_h, a.out_stride)
+        pix.append(out[:, : a.out_w * a.out_channels].astype(np.float32).ravel())
+        index.append((pix_base + i, off))
+        off += pix[-1].size
+    np.save(os.path.join(out_dir, f"pixels{tag}.npy"), np.concatenate(pix) if pix else np.zeros(0, np.float32))
+    np.save(os.path.join(out_dir, f"pixel_index{tag}.npy"), np.asarray(index, dtype=np.float64).reshape(-1, 2))
+    log(f"dumped {len(rec)} records and the pixels of {len(chosen)} images ({off * 4 / 1e6:.1f} MB) to {out_dir}")
+
 
 def run_batches(ctx, arrs, nimg, k0, count, on_done):
     """Batches k0 .. k0+count-1 of one rank, pipelined len(arrs) deep (the
@@ -302,7 +367,18 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="control plane only (no GPU, no library): every rank joins the rendezvous, rank 0 prints "
                          "one JSON line naming the ranks that joined (tests the launcher)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the oracle check of the last timed "
+                         "batch, the instrumented stage pass and the CPU baseline (--no-verify and "
+                         "--no-cpu-baseline drop one of them again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result records and a seeded sample of its "
+                         "output pixels as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: the timed steps and the result line only
+        args.no_verify = args.no_cpu_baseline = True
 
     # ---- ranks: an external launcher (torch.distributed.run) sets WORLD_SIZE;
     # without one, --gpus N > 1 starts its own N ranks before anything touches
@@ -404,6 +480,9 @@ def main():
     allv = comm.allgather_obj({"elapsed": el, "stats": stats,
                                "ncand": sum(last[i].n_candidates for i in range(nimg)),
                                "bad": bad[0]})
+    if args.dump_outputs:  # before anything else runs: the last timed batch's outputs are still in its slot
+        dump_outputs(ctx, args.dump_outputs, f"_rank{rank}" if world > 1 else "", [last],
+                     range(rank * nimg, (rank + 1) * nimg), last, 0)
     # correctness of the headline batch itself (untimed): the last timed batch's
     # records and outputs against the oracle, including images past 2^32 of pool
     vlast = (args.warmup + args.steps - 1) % PIPE_DEPTH
@@ -417,14 +496,16 @@ def main():
         if verr:
             log(f"rank {rank}: VERIFY FAILED {vok}/{vtot}: {verr}")
     allv_v = comm.allgather_obj({"ok": vok, "tot": vtot, "err": verr})
-    # stage split: an instrumented pass of a few more batches, every stage timed
-    n_stage = min(args.steps, 5)
-    run(args.warmup + args.steps, 3)  # clocks back up after the verification's idle GPU
-    ctx.set_timing(True)
-    ctx.reset_stats()
-    run(args.warmup + args.steps + 3, n_stage)
-    ctx.set_timing(False)
-    stage_stats = {k: ctx.stats(k) for k in ("batch", "resize", "sc_prep", "sc_score", "crop_apply")}
+    # stage split (--full): an instrumented pass of a few more batches, every stage timed
+    n_stage = min(args.steps, 5) if args.full else 0
+    stage_stats = {}
+    if args.full:
+        run(args.warmup + args.steps, 3)  # clocks back up after the verification's idle GPU
+        ctx.set_timing(True)
+        ctx.reset_stats()
+        run(args.warmup + args.steps + 3, n_stage)
+        ctx.set_timing(False)
+        stage_stats = {k: ctx.stats(k) for k in ("batch", "resize", "sc_prep", "sc_score", "crop_apply")}
     if rank == 0:
         T = max(v["elapsed"] for v in allv)
         mpix = world * nimg * W * H * args.steps / 1e6
@@ -471,15 +552,17 @@ def main():
             "stages_ms_per_step": dict(
                 {k: round(v[0] / max(v[1], 1), 4) for k, v in stage_stats.items()},
                 **{k: round(v[0] / max(v[1], 1), 4) for k, v in stats.items() if k.startswith("host_")}),
-            "stage_timing": f"stage ranges from an instrumented pass of {n_stage} further batches (every stage "
-                            "timed); the timed region times the resample stage only (roofline.avg_launch_ms), "
-                            "host_* over the timed region",
+            "stage_timing": (f"stage ranges from an instrumented pass of {n_stage} further batches (every stage "
+                             "timed); the timed region times the resample stage only (roofline.avg_launch_ms), "
+                             "host_* over the timed region") if args.full else
+                            ("host_* over the timed region, which times the resample stage only "
+                             "(roofline.avg_launch_ms); --full adds every stage's range from an instrumented pass"),
             "smartcrop_kernels": " + ".join(f"{SC_KERNEL_OF_PATH[p]} ({n} images)" for p, n in sc_paths.items() if n),
             "exact_rescored_crops_per_step": allv[0]["ncand"],
             "failed_images": sum(v["bad"] for v in allv),
             "verified": (f"{sum(v['ok'] for v in allv_v)}/{sum(v['tot'] for v in allv_v)} images of the last "
                          "timed batch vs the oracle (pixels +-1 LSB, crop box bit-exact on the GPU pixels)")
-                        if not args.no_verify else "skipped (--no-verify)",
+                        if not args.no_verify else "skipped (--no-verify, or a run without --full)",
         }
         if ablation:
             result["ablation"] = (f"FI_VR_VARIANT={os.environ.get('FI_VR_VARIANT')}: {ablation} profiling launches "
@@ -674,6 +757,9 @@ def run_cfg4(args, rank, world, local_rank, comm):
     stats = {k: ctx.stats(k) for k in names}
     paths = {p: ctx.stats(p)[1] // max(args.steps, 1) for p in KERNEL_OF_PATH}
     ablation = ctx.stats("vr_ablation")[1]
+    if args.dump_outputs and batches:  # every batch's records; pixels from the last batch, still in its dst slot
+        dump_outputs(ctx, args.dump_outputs, f"_rank{rank}" if world > 1 else "", arrs, np.concatenate(idx_of),
+                     arrs[-1], sum(len(b) for b in batches[:-1]))
     # correctness of the timed work itself (untimed): 16 images of this rank's
     # last batch, spread over it, against the oracle (each image its own size
     # class and op; smart-crop boxes bit-exact on the GPU pixels)
@@ -744,7 +830,7 @@ def run_cfg4(args, rank, world, local_rank, comm):
             "failed_images": sum(v["bad"] for v in allv),
             "verified": (f"{sum(v['vok'] for v in allv)}/{sum(v['vtot'] for v in allv)} images of each rank's last "
                          "batch vs the oracle (pixels +-1 LSB, crop box bit-exact on the GPU pixels)")
-                        if not args.no_verify else "skipped (--no-verify)",
+                        if not args.no_verify else "skipped (--no-verify, or a run without --full)",
         }
         if ablation:
             result["ablation"] = (f"FI_VR_VARIANT={os.environ.get('FI_VR_VARIANT')}: {ablation} profiling launches "

@@ -1,6 +1,6 @@
 """Checker for device-resident batches (TEST INFRASTRUCTURE, like the rest of
 oracle/): compares images of a batch the GPU path produced with the CPU
-oracle.  Used by bench.py after its timed loop (the headline batch itself) and
+oracle.  Used by bench.py --full after its timed loop (the headline batch itself) and
 by tests/test_gpu_parity.py; never by the product path."""
 from __future__ import annotations
 

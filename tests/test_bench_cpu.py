@@ -142,6 +142,43 @@ def test_batch_loop_pipelines_and_gathers_once_without_blocking(tmp_path):
     assert [r[0] for r in got0] == [r * 100 + j for r in (0, 1) for j in range(steps * nimg)]
 
 
+def test_dump_outputs_writes_records_and_a_fixed_pixel_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every image's record, and the unpadded pixels of a
+    seeded sample of the last batch within the byte budget -- the same sample
+    on every call, failed images left out."""
+    import numpy as np
+
+    n, w, h, stride = 6, 5, 3, 16
+    arr = (L.FiImage * n)()
+    mem = {}
+    for i in range(n):
+        a = arr[i]
+        a.dst, a.out_w, a.out_h, a.out_channels, a.out_stride = 4096 * (i + 1), w, h, 3, stride
+        a.crop_x, a.crop_score, a.n_candidates, a.status = i, 0.5 * i, 1, (5 if i == 2 else 0)
+        mem[a.dst] = (np.arange(h * stride) + 7 * i).astype(np.uint8)
+
+    class Ctx:
+        def d2h(self, p, nbytes):
+            assert nbytes == h * stride
+            return mem[p].copy()
+
+    monkeypatch.setattr(bench, "DUMP_PIXEL_BYTES", 3 * w * h * 3 * 4)  # room for three images
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(Ctx(), str(tmp_path / d), "", [arr], range(100, 100 + n), arr, 0)
+        got.append({f: np.load(tmp_path / d / f"{f}.npy") for f in ("records", "pixels", "pixel_index")})
+    rec, pix, idx = (got[0][f] for f in ("records", "pixels", "pixel_index"))
+    assert all(np.array_equal(got[0][f], got[1][f]) for f in got[0])
+    assert rec.dtype == np.float64 and rec.shape == (n, 1 + len(bench.DUMP_RECORD_FIELDS))
+    assert list(rec[:, 0]) == list(range(100, 100 + n))
+    assert list(rec[:, 1 + bench.DUMP_RECORD_FIELDS.index("crop_score")]) == [0.5 * i for i in range(n)]
+    assert pix.dtype == np.float32 and pix.size == 3 * w * h * 3 and idx.shape == (3, 2)
+    assert 2 not in idx[:, 0] and list(idx[:, 0]) == sorted(set(idx[:, 0]))
+    for row, off in idx.astype(int):
+        want = mem[arr[row].dst].reshape(h, stride)[:, : w * 3].ravel()
+        assert np.array_equal(pix[off:off + w * h * 3], want)
+
+
 def _bench(args, **env):
     import subprocess
 

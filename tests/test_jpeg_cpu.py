@@ -1,12 +1,15 @@
 """fi_jpeg_info (host-only header parse of the GPU JPEG decoder): the streams
 it takes and the ones it leaves to the host decoder."""
 import io
+import os
 
 import pytest
 from PIL import Image
 
 from flyimg_amd.runtime import jpeg_info
 from flyimg_amd.synth import synth_rgb
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _enc(img, mode=None, **kw):
@@ -37,7 +40,7 @@ def test_jpeg_info_host_fallback(kw, mode):
 def test_jpeg_info_malformed():
     for blob in (b"", b"\xff\xd8", b"\x89PNG\r\n\x1a\n" + b"\0" * 16, b"\xff\xd8\xff\xc0\x00\x11"):
         assert jpeg_info(blob) is None
-    with open("tests/golden/smart_crop.jpg", "rb") as f:  # the reference fixture is progressive
+    with open(os.path.join(ROOT, "tests/golden/smart_crop.jpg"), "rb") as f:  # the reference fixture is progressive
         assert jpeg_info(f.read()) is None
 
 
@@ -57,7 +60,7 @@ def test_jpeg_info_oversubscribed_huffman_table_in_child():
     good = _enc(synth_rgb(64, 48, 5), quality=90)
     k = good.index(b"\xff\xda")  # after the encoder's own DHTs: this table is the one in force
     bad = good[:k] + _dht(0x00, [40] + [0] * 15, range(40)) + good[k:]
-    code = ("import sys; sys.path.insert(0, '.');"
+    code = ("import sys; sys.path.insert(0, sys.argv[2]);"
             "from flyimg_amd.runtime import jpeg_info;"
             "print(jpeg_info(open(sys.argv[1], 'rb').read()))")
     import tempfile
@@ -65,7 +68,7 @@ def test_jpeg_info_oversubscribed_huffman_table_in_child():
     with tempfile.NamedTemporaryFile(suffix=".jpg", delete=False) as f:
         f.write(bad)
         path = f.name
-    r = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([sys.executable, "-c", code, path, ROOT], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     assert r.stdout.strip() == "None"
 

@@ -8,7 +8,7 @@ mkdir -p $OUT
 for i in ${AB_ROUNDS-1 2 3}; do
   for v in A B; do
     if [ $v = A ]; then export FI_LIB_PATH=$PWD/tools/bin/libA.so; else unset FI_LIB_PATH; fi
-    timeout -k 10 240 python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/$v$i.json 2> $OUT/$v$i.err || exit $?
+    timeout -k 10 240 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/$v$i.json 2> $OUT/$v$i.err || exit $?
     python3 -c "import json; d=json.load(open('$OUT/$v$i.json')); s=d['stages_ms_per_step']; print('$v$i', 'step', d['ms_per_step'], ' '.join(f'{k} {s[k]}' for k in ('resize','sc_prep','sc_score','crop_apply')))"
   done
 done

@@ -12,15 +12,15 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -rf --timeout 300 --timeou
 echo "pytest rc=$rc"; tail -3 "$OUT/pytest_gpu.log"; ok $rc || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; rc=$?
 echo "smoke rc=$rc"; tail -2 "$OUT/smoke.log"; ok $rc || exit $rc
-timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
+timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
 echo "bench rc=$rc"; cat "$OUT/bench.json"; ok $rc || exit $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-  python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/profile_bench.json" 2> "$OUT/prof.err"; rc=$?
+  python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/profile_bench.json" 2> "$OUT/prof.err"; rc=$?
 echo "rocprof rc=$rc"; ok $rc || exit $rc
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 180 rocprofv3 --pmc $c --kernel-include-regex "k_rs_vr" --output-format csv -d "$OUT/pmc_$c" -o run -- \
-    python3 "$ROOT/bench.py" --steps 1 --warmup 1 --images 512 --no-cpu-baseline > "$OUT/pmc_$c.json" 2> "$OUT/pmc_$c.err" || exit $?
+    python3 "$ROOT/bench.py" --full --steps 1 --warmup 1 --images 512 --no-cpu-baseline > "$OUT/pmc_$c.json" 2> "$OUT/pmc_$c.err" || exit $?
 done
 python3 "$ROOT/tools/pmc_to_json.py" "$OUT" k_rs_vr 512 "$OUT/traffic_cfg2_k_rs_vr.json"
 cd "$ROOT"

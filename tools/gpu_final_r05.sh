@@ -22,7 +22,7 @@ if [ "${PART:-1}" = 1 ]; then
     n=512; [ $wl = cfg3 ] && n=256
     for c in FETCH_SIZE WRITE_SIZE; do
       timeout -s KILL 180 rocprofv3 --pmc $c --kernel-include-regex "k_rs_vr" --output-format csv -d "$OUT/pmc_${wl}/$c" -o run -- \
-        python3 "$ROOT/bench.py" --workload $wl --steps 1 --warmup 1 --images $n --no-cpu-baseline \
+        python3 "$ROOT/bench.py" --full --workload $wl --steps 1 --warmup 1 --images $n --no-cpu-baseline \
         > "$OUT/pmc_${wl}_$c.json" 2> "$OUT/pmc_${wl}_$c.err" || { echo "pmc $wl $c rc=$?"; exit 5; }
     done
     python3 "$ROOT/tools/pmc_to_json.py" "$OUT/pmc_$wl" k_rs_vr $n "$OUT/traffic_${wl}_k_rs_vr.json" || exit 4
@@ -34,7 +34,7 @@ if [ "${PART:-1}" = 3 ]; then
   cd /tmp && export TMPDIR=/tmp
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 500 rocprofv3 --pmc $c --kernel-include-regex "k_rs_" --output-format csv -d "$OUT/pmc_cfg4/$c" -o run -- \
-      python3 "$ROOT/bench.py" --workload cfg4 --steps 1 --warmup 1 --no-cpu-baseline --no-verify \
+      python3 "$ROOT/bench.py" --full --workload cfg4 --steps 1 --warmup 1 --no-cpu-baseline --no-verify \
       > "$OUT/pmc_cfg4_$c.json" 2> "$OUT/pmc_cfg4_$c.err" || { echo "pmc cfg4 $c rc=$?"; exit 5; }
   done
   # every resample dispatch of the warm-up and the timed step: 2 x the shard
@@ -46,19 +46,19 @@ fi
 if [ "${PART:-1}" = 2 ]; then
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_cfg2" -o run -- \
-    python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/prof_cfg2.json" 2> "$OUT/prof_cfg2.err" || exit 6
+    python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/prof_cfg2.json" 2> "$OUT/prof_cfg2.err" || exit 6
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_cfg3" -o run -- \
-    python3 "$ROOT/bench.py" --workload cfg3 --steps 6 --warmup 2 --no-cpu-baseline > "$OUT/prof_cfg3.json" 2> "$OUT/prof_cfg3.err" || exit 6
+    python3 "$ROOT/bench.py" --full --workload cfg3 --steps 6 --warmup 2 --no-cpu-baseline > "$OUT/prof_cfg3.json" 2> "$OUT/prof_cfg3.err" || exit 6
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_cfg4" -o run -- \
-    python3 "$ROOT/bench.py" --workload cfg4 --steps 1 --warmup 1 --no-cpu-baseline > "$OUT/prof_cfg4.json" 2> "$OUT/prof_cfg4.err" || exit 6
+    python3 "$ROOT/bench.py" --full --workload cfg4 --steps 1 --warmup 1 --no-cpu-baseline > "$OUT/prof_cfg4.json" 2> "$OUT/prof_cfg4.err" || exit 6
   echo "rocprof ok"
   cd "$ROOT"
-  timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
+  timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
   echo "bench rc=$rc"; cat "$OUT/bench.json"; [ $rc -eq 0 ] || exit $rc
   for wl in cfg1 cfg3 cfg5; do
-    timeout -k 10 600 python bench.py --workload $wl > "$OUT/$wl.json" 2> "$OUT/$wl.err" || { echo "$wl failed"; tail -3 "$OUT/$wl.err"; exit 3; }
+    timeout -k 10 600 python bench.py --full --workload $wl > "$OUT/$wl.json" 2> "$OUT/$wl.err" || { echo "$wl failed"; tail -3 "$OUT/$wl.err"; exit 3; }
     python3 -c "import json;d=json.load(open('$OUT/$wl.json'));print('$wl', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline'].get('traffic'), d.get('verified','')[:5])"
   done
-  timeout -k 10 900 python bench.py --workload cfg4 --steps 1 --warmup 1 > "$OUT/cfg4.json" 2> "$OUT/cfg4.err" || { echo "cfg4 failed"; tail -3 "$OUT/cfg4.err"; exit 3; }
+  timeout -k 10 900 python bench.py --full --workload cfg4 --steps 1 --warmup 1 > "$OUT/cfg4.json" 2> "$OUT/cfg4.err" || { echo "cfg4 failed"; tail -3 "$OUT/cfg4.err"; exit 3; }
   python3 -c "import json;d=json.load(open('$OUT/cfg4.json'));print('cfg4', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline'].get('traffic'), d.get('verified','')[:5])"
 fi

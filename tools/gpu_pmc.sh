@@ -12,7 +12,7 @@ ARGS=${PMC_BENCH_ARGS:---steps 1 --warmup 1 --images 512 --no-cpu-baseline}
 pass() {
   local name=$1; shift
   timeout -s KILL 150 rocprofv3 --pmc "$@" --kernel-include-regex "$REGEX" --output-format csv -d "$OUT/$name" -o run -- \
-    python "$ROOT/bench.py" $ARGS > "$OUT/$name.bench.json" 2> "$OUT/$name.err"; local rc=$?
+    python "$ROOT/bench.py" --full $ARGS > "$OUT/$name.bench.json" 2> "$OUT/$name.err"; local rc=$?
   echo "pass $name rc=$rc"; return $rc
 }
 pass sq SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES || exit $?

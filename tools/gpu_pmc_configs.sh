@@ -15,7 +15,7 @@ for w in ${WORKLOADS:-cfg2 cfg1 cfg3 cfg5}; do
   n=512; [ "$w" = cfg3 ] && n=1024
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 240 rocprofv3 --pmc $c --kernel-include-regex "$K" --output-format csv -d "$OUT/${w}_$c" -o run -- \
-      python3 "$ROOT/bench.py" --workload $w --steps 1 --warmup 1 --images $n --no-cpu-baseline \
+      python3 "$ROOT/bench.py" --full --workload $w --steps 1 --warmup 1 --images $n --no-cpu-baseline \
       > "$OUT/${w}_$c.json" 2> "$OUT/${w}_$c.err" || { echo "$w $c rc=$?"; tail -3 "$OUT/${w}_$c.err"; exit 3; }
   done
   mkdir -p "$OUT/$w" && mv "$OUT/${w}_FETCH_SIZE" "$OUT/${w}_WRITE_SIZE" "$OUT/$w/"

@@ -10,7 +10,7 @@ for v in ${VARIANTS:-0}; do
   export FI_VR_VARIANT=$v
   timeout -s KILL 120 rocprofv3 --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU \
     --kernel-include-regex k_rs_vr --output-format csv -d "$OUT/v$v" -o run -- \
-    python3 "$ROOT/bench.py" --steps 1 --warmup 1 --images 512 --no-cpu-baseline --no-verify > "$OUT/v$v.json" 2> "$OUT/v$v.err" || { echo "pmc v$v rc=$?"; exit 5; }
+    python3 "$ROOT/bench.py" --full --steps 1 --warmup 1 --images 512 --no-cpu-baseline --no-verify > "$OUT/v$v.json" 2> "$OUT/v$v.err" || { echo "pmc v$v rc=$?"; exit 5; }
   python3 - "$OUT/v$v" <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True)

@@ -24,20 +24,20 @@ for s in ${STEP:-tests bench trace}; do
   bench)
     # FI_SC_CX=1: smartcrop prescale beside the next resample (default); 0: k_sc_fd serial
     for cx in ${CXS:-1 0}; do
-      FI_SC_CX=$cx timeout -k 10 300 python bench.py --no-cpu-baseline --steps ${STEPS:-20} ${WL:+--workload $WL} \
+      FI_SC_CX=$cx timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps ${STEPS:-20} ${WL:+--workload $WL} \
         > "$OUT/bench_cx$cx.json" 2> "$OUT/bench_cx$cx.err"; rc=$?
       [ $rc -eq 0 ] || { echo "bench cx=$cx rc=$rc"; tail -5 "$OUT/bench_cx$cx.err"; exit $rc; }
       python3 -c "import json;d=json.load(open('$OUT/bench_cx$cx.json'));print('cx=$cx', d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'], d['stages_ms_per_step'], d['smartcrop_kernels'], d['verified'][:5])"
     done ;;
   cfg4)
-    timeout -k 10 600 python bench.py --workload cfg4 --steps 1 --warmup 1 --no-cpu-baseline > "$OUT/cfg4.json" \
+    timeout -k 10 600 python bench.py --full --workload cfg4 --steps 1 --warmup 1 --no-cpu-baseline > "$OUT/cfg4.json" \
       2> "$OUT/cfg4.err"; rc=$?
     [ $rc -eq 0 ] || { echo "cfg4 rc=$rc"; tail -5 "$OUT/cfg4.err"; exit $rc; }
     python3 -c "import json;d=json.load(open('$OUT/cfg4.json'));print('cfg4', d['value'], d['ms_per_step'], d['roofline']['frac'], d['verified'][:5]); print({k: v for k, v in d['stages_ms_per_step'].items() if k.startswith('host') or k in ('resize','sc_prep','sc_score','batch')})" ;;
   trace)
     cd /tmp && export TMPDIR=/tmp
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-      python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-verify > "$OUT/trace.json" 2> "$OUT/trace.err"; rc=$?
+      python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-verify > "$OUT/trace.json" 2> "$OUT/trace.err"; rc=$?
     cd "$ROOT"
     [ $rc -eq 0 ] || { echo "trace rc=$rc"; tail -5 "$OUT/trace.err"; exit $rc; }
     f=$(find "$OUT/trace" -name "*kernel_stats.csv" | head -1)

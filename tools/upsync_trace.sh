@@ -1,7 +1,8 @@
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r06; mkdir -p $OUT
 for u in 1 0; do
-FI_UP_SYNC=$u timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/up$u" -o run -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-verify > "$OUT/up$u.json" 2> "$OUT/up$u.err" || exit 1
+FI_UP_SYNC=$u timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/up$u" -o run -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-verify > "$OUT/up$u.json" 2> "$OUT/up$u.err" || exit 1
 python3 $GRAFT_REPO_ROOT/tools/trace_gaps.py "$OUT/up$u" > "$OUT/up$u.txt"
 python3 - "$OUT/up$u.txt" $u <<'PY'
 import sys, re

@@ -8,7 +8,7 @@ if [ "${TESTS:-1}" = 1 ]; then
     > $OUT/pytest.log 2>&1; rc=$?; tail -2 $OUT/pytest.log; [ $rc -eq 0 ] || exit $rc
 fi
 for f in ${FORKS:-0 1 0 1}; do
-  FI_VR_FORK=$f timeout -k 10 400 python bench.py --workload cfg4 --steps 2 --warmup 1 --no-cpu-baseline \
+  FI_VR_FORK=$f timeout -k 10 400 python bench.py --full --workload cfg4 --steps 2 --warmup 1 --no-cpu-baseline \
     > $OUT/f$f.json 2> $OUT/f$f.err || { echo "fork $f rc=$?"; tail -3 $OUT/f$f.err; exit 3; }
   python3 -c "import json;d=json.load(open('$OUT/f$f.json'));s=d['stages_ms_per_step'];print('fork', $f, d['value'], d['ms_per_step'], d['roofline']['frac'], s.get('resize'), d.get('verified','')[:6])"
 done
