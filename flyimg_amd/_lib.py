@@ -193,6 +193,8 @@ def lib():
     L.fi_debug_host_plan.argtypes = [ctypes.POINTER(FiImage), i32, i32, ctypes.POINTER(ctypes.c_double)]
     L.fi_jpeg_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(i32), P(i32), P(i32)]
     L.fi_jpeg_decode_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp]
+    L.fi_jpeg_encode_bound.argtypes = [i32, i32, i32, i32, i32, P(ctypes.c_size_t)]
+    L.fi_jpeg_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     _lib = L
     return L
 

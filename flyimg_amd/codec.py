@@ -12,7 +12,11 @@ ImageHandler::processNewImage end to end for a batch of encoded images.
            ImageProcessor.php:195-217); neither ``cjpeg`` nor ``convert`` is
            in this image, so the encoder is libjpeg-turbo at the same quality
            (IM's own JPEG coder is libjpeg as well).  Images with alpha are
-           written as PNG.
+           written as PNG.  With ``gpu_encode`` the JPEGs are written on the
+           MI355X instead (fi_jpeg_encode_device): the outputs stay in device
+           memory and leave it compressed -- the same baseline coding with
+           one restart interval per MCU row, byte for byte what
+           libjpeg-turbo writes with ``restart_marker_rows=1``.
 
 Gray (L), bilevel and palette sources are expanded to RGB / RGBA before the
 GPU (IM would keep a gray JPEG gray: the channels are equal either way), and
@@ -130,12 +134,20 @@ class CodecPipeline:
     """Batches of encoded images through decode -> GPU -> encode.  With
     ``gpu_decode`` (default) baseline gray / YCbCr JPEGs are decoded on the MI355X
     straight into device memory (bit-exact with the host decoder) and only
-    the other sources take the host decoder."""
+    the other sources take the host decoder.  With ``gpu_encode`` (off by
+    default: the files carry restart markers, so their bytes differ from the
+    host encoder's, the decoded pixels do not) ``process`` keeps the outputs
+    on the device and writes every JPEG there with one fi_jpeg_encode_device
+    call; outputs with alpha still go through the host PNG writer."""
 
-    def __init__(self, ctx, threads: int = 16, gpu_decode: bool = True):
+    def __init__(self, ctx, threads: int = 16, gpu_decode: bool = True, gpu_encode: bool = False):
         self.ctx = ctx
         self.pool = ThreadPoolExecutor(max_workers=max(1, threads))
         self.gpu_decode = gpu_decode
+        self.gpu_encode = gpu_encode
+        # ``process``: host seconds in the encode stage, the bytes its outputs
+        # were as pixels and are as files (with gpu_encode, what crosses PCIe)
+        self.process_stats = {"s_encode": 0.0, "raw_bytes": 0, "encoded_bytes": 0}
 
     def close(self):
         self.pool.shutdown()
@@ -159,10 +171,13 @@ class CodecPipeline:
         outs, recs, _ = self.ctx.process(srcs, ops)
         return outs, list(recs)
 
-    def _gpu_batch(self, blobs, bags, dims):
+    def _gpu_batch(self, blobs, bags, dims, held=None):
         """GPU decode into one device pool (16-B aligned rows for the streaming
         resample kernels), one device batch.
-        Returns (outputs, records, indices the GPU decoder turned down)."""
+        Returns (outputs, records, indices the GPU decoder turned down).  With
+        ``held`` (a list) the outputs stay on the device: they come back as
+        (device pointer, w, h, stride, channels) views and their allocation is
+        appended to ``held`` for the caller to free."""
         strides = [(w * 3 + 15) // 16 * 16 for w, _, _ in dims]
         offs = np.concatenate([[0], np.cumsum([(s * h + 255) // 256 * 256 for s, (_, h, _) in zip(strides, dims)])])
         base = self.ctx.malloc(int(offs[-1]))
@@ -179,7 +194,11 @@ class CodecPipeline:
                     op.flags |= L.FI_SRC_PSEUDOCLASS
                 ops.append(op)
                 keep.append(i)
-            outs, recs, _ = self.ctx.process_device_views(views, ops)
+            if held is None:
+                outs, recs, _ = self.ctx.process_device_views(views, ops)
+            else:
+                obase, outs, recs, _ = self.ctx.process_device_resident(views, ops)
+                held.append(obase)
         finally:
             self.ctx.free(base)
         full_o, full_r = [None] * len(blobs), [None] * len(blobs)
@@ -187,9 +206,48 @@ class CodecPipeline:
             full_o[i], full_r[i] = outs[k], recs[k]
         return full_o, full_r, [i for i in range(len(blobs)) if status[i] != L.FI_OK]
 
+    def _gpu_encode(self, outs, quality, held):
+        """Every JPEG output in one fi_jpeg_encode_device call: device views
+        as they are, host arrays (host-decoded sources) uploaded first; chroma
+        as ``encode``: q >= 90 -> 4:4:4, else 4:2:0.  Alpha outputs: host PNG."""
+        encoded = [None] * len(outs)
+        views, idx = [], []
+        for i, o in enumerate(outs):
+            if isinstance(o, tuple):  # a device batch's output (RGB sources: 1 or 3 channels)
+                view = o
+            else:
+                ch = o.shape[2] if o.ndim == 3 else 1
+                if ch in (2, 4):
+                    encoded[i] = encode(o, quality[i])
+                    continue
+                o = np.ascontiguousarray(o)
+                p = self.ctx.malloc(max(o.nbytes, 1))
+                held.append(p)
+                self.ctx.h2d(p, o)
+                view = (p, o.shape[1], o.shape[0], o.shape[1] * ch, ch)
+            views.append(view)
+            idx.append(i)
+        qs = [int(quality[i]) for i in idx]
+        files = self.ctx.jpeg_encode(views, qs, [0 if q >= 90 else 2 for q in qs])
+        for i, f in zip(idx, files):
+            if f is None:
+                msg = L.lib().fi_last_error()
+                raise ExecFailedException("Command failed.\nThe exit code: %d\n%s" % (
+                    L.FI_EINVAL, msg.decode() if msg else f"image {i}: JPEG encode"))
+            encoded[i] = f
+        return encoded
+
     def process(self, blobs: list[bytes], options: list[str]):
         """Returns (encoded outputs, fi_image records); a failed image raises
         ExecFailedException as Processor::execute does."""
+        held = []  # device allocations that live until the GPU encode
+        try:
+            return self._process(blobs, options, held)
+        finally:
+            for p in held:
+                self.ctx.free(p)
+
+    def _process(self, blobs, options, held):
         bags = [OptionsBag(o) for o in options]
         n = len(blobs)
         outs, recs = [None] * n, [None] * n
@@ -201,7 +259,8 @@ class CodecPipeline:
         host = [i for i in range(n) if dims[i] is None]
         gpu = [i for i in range(n) if dims[i] is not None]
         if gpu:
-            o, r, back = self._gpu_batch([blobs[i] for i in gpu], [bags[i] for i in gpu], [dims[i] for i in gpu])
+            o, r, back = self._gpu_batch([blobs[i] for i in gpu], [bags[i] for i in gpu], [dims[i] for i in gpu],
+                                         held if self.gpu_encode else None)
             for k, i in enumerate(gpu):
                 outs[i], recs[i] = o[k], r[k]
             host += [gpu[k] for k in back]
@@ -214,7 +273,17 @@ class CodecPipeline:
                 msg = L.lib().fi_last_error()
                 raise ExecFailedException("Command failed.\nThe exit code: %d\n%s" % (
                     r.status, msg.decode() if msg else f"image {i}"))
-        encoded = list(self.pool.map(lambda a: encode(a[0], a[1]), zip(outs, [self._quality(b) for b in bags])))
+        import time
+
+        quality = [self._quality(b) for b in bags]
+        t0 = time.perf_counter()
+        if self.gpu_encode:
+            encoded = self._gpu_encode(outs, quality, held)
+        else:
+            encoded = list(self.pool.map(lambda a: encode(a[0], a[1]), zip(outs, quality)))
+        self.process_stats["s_encode"] += time.perf_counter() - t0
+        self.process_stats["raw_bytes"] += sum(r.out_w * r.out_h * r.out_channels for r in recs)
+        self.process_stats["encoded_bytes"] += sum(len(e) for e in encoded)
         return encoded, recs
 
     def _prepare(self, slot, blobs, options):
@@ -240,7 +309,9 @@ class CodecPipeline:
         """Pipelined form of ``process`` over an iterable of (blobs, options)
         batches: batch k+1 is decoded into pinned memory and submitted
         (fi_submit_batch) while batch k's DMA and kernels run, and batch k is
-        encoded while batch k+1 runs.  Yields (encoded outputs, records) per
+        encoded while batch k+1 runs (on the host encoder: ``gpu_encode``
+        applies to ``process`` only -- this form's outputs are already in pinned
+        host memory when the batch ends).  Yields (encoded outputs, records) per
         batch, in order; the ``stats`` attribute holds the host time spent
         decoding, blocked on the GPU, and encoding."""
         from .runtime import plan as fi_plan

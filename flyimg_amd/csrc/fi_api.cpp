@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "fi_internal.h"
+#include "fi_jpeg_enc.h"
 #include "fi_plan.h"
 
 namespace fi {
@@ -63,6 +64,11 @@ int jpeg_info(const uint8_t *data, size_t len, int *w, int *h, int *c);
 int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *len, int n, uint8_t *const *dst,
                       const int64_t *dst_stride, int out_channels, int32_t *status,
                       void *(*alloc)(void *, int, size_t), void *actx, std::string *err);
+int jpeg_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                      const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
+                      const int32_t *subsampling, int n, uint8_t *const *out, const size_t *out_cap, size_t *out_len,
+                      int32_t *status, void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *),
+                      void *actx, std::string *err);
 int launch_sc_score(hipStream_t s, int mode, const ScDesc *descs, int n, size_t lds, const DevCrop *crops,
                     const double *ad, CropScore *scores, ScResult *results, const ScParamsDev &P, const int32_t *ai);
 int launch_sc_score3(hipStream_t s, const ScDesc *descs, int n, size_t lds, const DevCrop *crops, const ScGroup *groups,
@@ -310,6 +316,10 @@ struct fi_ctx {
   DevBuf jpeg[3];           // GPU JPEG decode: upload (compressed data + tables), -, coefficients + planes
   void *jpeg_host = nullptr;  // its pinned staging
   size_t jpeg_host_cap = 0;
+  DevBuf jpeg_enc[3];       // GPU JPEG encode: upload (tables + headers), coefficients + slots, packed streams
+  void *jpeg_enc_host = nullptr;  // its pinned staging (upload, then download)
+  size_t jpeg_enc_host_cap = 0;
+  struct Timer *jpeg_enc_timer = nullptr;  // the encode kernel being timed (fi_jpeg_encode_device)
   std::string skinsat_key;
   HashMap<const AxisTable *, VmV> vmv_cache;   // ok iff nblk > 0
   HashMap<const AxisTable *, VrV> vrv_cache;   // ok iff nblk > 0
@@ -3206,6 +3216,53 @@ int fi_jpeg_decode_device(fi_ctx *c, const uint8_t *const *data, const size_t *l
                      status[i] == FI_EUNSUPPORTED ? "JPEG stream the GPU decoder does not handle" : "malformed JPEG");
   return FI_OK;
 }
+// GPU JPEG encode (fi_jpeg_enc.hip): the write half of `convert` (IM writes the
+// output with libjpeg) on the device
+int fi_jpeg_encode_bound(int32_t w, int32_t h, int32_t channels, int32_t quality, int32_t subsampling, size_t *bytes) {
+  if (!bytes) return set_err(FI_EINVAL, "bad arguments");
+  const int rc = jpeg_enc_bound(w, h, channels, quality, subsampling, bytes);
+  if (rc)
+    return set_err(rc, rc == FI_EUNSUPPORTED ? "channel count or subsampling the GPU JPEG encoder does not write"
+                                             : "bad JPEG dimensions or quality");
+  return FI_OK;
+}
+static void *jpeg_enc_alloc(void *actx, int which, size_t bytes) {
+  fi_ctx *c = static_cast<fi_ctx *>(actx);
+  if (which == 3)  // pinned host staging (no copy of an earlier request is in flight: see jpeg_encode_batch)
+    return ensure_pinned_buf(&c->jpeg_enc_host, &c->jpeg_enc_host_cap, bytes) == FI_OK ? c->jpeg_enc_host : nullptr;
+  return ensure(c, &c->jpeg_enc[which], bytes) == FI_OK ? c->jpeg_enc[which].p : nullptr;
+}
+static void jpeg_enc_stage(void *actx, const char *name) {  // ends the running kernel's range, starts `name`'s
+  fi_ctx *c = static_cast<fi_ctx *>(actx);
+  delete c->jpeg_enc_timer;
+  c->jpeg_enc_timer = name ? new Timer(c, name, 0) : nullptr;
+}
+int fi_jpeg_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                          const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
+                          const int32_t *subsampling, int32_t n, uint8_t *const *out, const size_t *out_cap,
+                          size_t *out_len, int32_t *status) {
+  if (!c || n < 0 ||
+      (n > 0 && (!src || !w || !h || !channels || !src_stride || !quality || !subsampling || !out || !out_cap ||
+                 !out_len || !status)))
+    return set_err(FI_EINVAL, "bad arguments");
+  if (n == 0) return FI_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
+  std::string err;
+  const int rc = jpeg_encode_batch(c->stream, src, w, h, channels, src_stride, quality, subsampling, n, out, out_cap,
+                                   out_len, status, jpeg_enc_alloc, jpeg_enc_stage, c, &err);
+  jpeg_enc_stage(c, nullptr);
+  collect_timers(c);
+  if (rc) return set_err(rc, "%s", err.c_str());
+  for (int i = 0; i < n; i++)  // the others are encoded
+    if (status[i])
+      return set_err(status[i], "image %d: %s", i,
+                     status[i] == FI_EUNSUPPORTED ? "channel count or subsampling the GPU JPEG encoder does not write"
+                     : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
+                                                  : "bad JPEG source, dimensions or quality");
+  return FI_OK;
+}
 // Test hook: the skin / saturation table of k_sc_fz<true> / k_sc_fd for `params`,
 // returned in r-major colour order (the device table is in sc_colour_key order)
 int fi_debug_skinsat(fi_ctx *c, const fi_smartcrop_params *params, uint16_t *out) {
@@ -3439,10 +3496,11 @@ void fi_destroy(fi_ctx *c) {
   sync_streams(c);
   if (c->comm) ncclCommDestroy(c->comm);
   for (DevBuf *b : {&c->arena, &c->work, &c->io, &c->gather, &c->pix, &c->skinsat, &c->jpeg[0], &c->jpeg[1],
-                    &c->jpeg[2]})
+                    &c->jpeg[2], &c->jpeg_enc[0], &c->jpeg_enc[1], &c->jpeg_enc[2]})
     if (b->p) (void)hipFree(b->p);
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->jpeg_host) (void)hipHostFree(c->jpeg_host);
+  if (c->jpeg_enc_host) (void)hipHostFree(c->jpeg_enc_host);
   for (Slot &sl : c->slots) {
     if (sl.blob) (void)hipHostFree(sl.blob);
     if (sl.res) (void)hipHostFree(sl.res);

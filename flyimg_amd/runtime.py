@@ -75,6 +75,15 @@ def jpeg_info(blob: bytes):
     return (w.value, h.value, c.value) if rc == L.FI_OK else None
 
 
+def jpeg_encode_bound(w: int, h: int, channels: int, quality: int, subsampling: int = 0) -> int:
+    """fi_jpeg_encode_bound: an upper bound of the GPU encoder's file size for
+    any image of this geometry (host only); raises FiError for arguments the
+    encoder turns down."""
+    n = ctypes.c_size_t()
+    L.check(L.lib().fi_jpeg_encode_bound(w, h, channels, quality, subsampling, ctypes.byref(n)))
+    return n.value
+
+
 class Context:
     def __init__(self, device: int = 0):
         self._lib = L.lib()
@@ -299,12 +308,101 @@ class Context:
             for p in ptrs:
                 self.free(p)
 
-    def process_device_views(self, views, ops: list[Op]):
+    def _jpeg_encode_call(self, views, qs, ss, ptrs, caps):
+        n = len(views)
+        I32, I64, SZ, VP = ctypes.c_int32 * n, ctypes.c_int64 * n, ctypes.c_size_t * n, ctypes.c_void_p * n
+        out_len, status = SZ(), I32()
+        rc = self._lib.fi_jpeg_encode_device(
+            self.h, VP(*[v[0] for v in views]), I32(*[v[1] for v in views]), I32(*[v[2] for v in views]),
+            I32(*[v[4] for v in views]), I64(*[v[3] for v in views]), I32(*qs), I32(*ss), n,
+            VP(*ptrs), SZ(*caps), out_len, status)
+        return rc, list(status), list(out_len)
+
+    def _jpeg_bound(self, view, q, s):
+        b = ctypes.c_size_t()
+        return b.value if self._lib.fi_jpeg_encode_bound(view[1], view[2], view[4], q, s, ctypes.byref(b)) == L.FI_OK else 1
+
+    def jpeg_encode_raw(self, views, quality, subsampling, caps=None):
+        """fi_jpeg_encode_device on (device pointer, w, h, stride, channels)
+        views; ``quality`` / ``subsampling`` per image or one value for all;
+        ``caps``: output capacities (default: fi_jpeg_encode_bound, 1 where the
+        bound turns the image down).  Returns (rc, status list, length list,
+        output buffer list): buffer i is a uint8 array of caps[i] + 64 bytes
+        whose last 128 are set to 0xA5 beforehand, so a caller can see what
+        was written behind the file and behind the capacity."""
+        n = len(views)
+        qs = list(quality) if isinstance(quality, (list, tuple)) else [quality] * n
+        ss = list(subsampling) if isinstance(subsampling, (list, tuple)) else [subsampling] * n
+        if caps is None:
+            caps = [self._jpeg_bound(v, q, s) for v, q, s in zip(views, qs, ss)]
+        offs = np.concatenate([[0], np.cumsum([c + 64 for c in caps])]).astype(np.int64)
+        pool = np.empty(int(offs[-1]), np.uint8)
+        bufs = [pool[int(offs[i]):int(offs[i + 1])] for i in range(n)]
+        for b, c in zip(bufs, caps):
+            b[max(0, c - 64):] = 0xA5
+        rc, status, lens = self._jpeg_encode_call(views, qs, ss, [b.ctypes.data for b in bufs], caps)
+        return rc, status, lens, bufs
+
+    def jpeg_encode(self, views, quality, subsampling) -> list[bytes | None]:
+        """fi_jpeg_encode_device: baseline JPEG files of device-resident images
+        given as (device pointer, w, h, stride, channels) views -- byte for
+        byte what Pillow writes with quality / subsampling (0 = 4:4:4, 2 =
+        4:2:0; per image or one value) and restart_marker_rows=1.  None where
+        the encoder turned the image down (alpha channels, other samplings,
+        bad quality).  The output buffers are sized to the pixels (the worst
+        case of fi_jpeg_encode_bound is many times a real file); the rare file
+        larger than its pixels -- noise at the top qualities -- is encoded
+        again into a buffer of the size the first call reported."""
+        n = len(views)
+        if not n:
+            return []
+        qs = list(quality) if isinstance(quality, (list, tuple)) else [quality] * n
+        ss = list(subsampling) if isinstance(subsampling, (list, tuple)) else [subsampling] * n
+        caps = [min(self._jpeg_bound(v, q, s), v[1] * v[2] * v[4] + 1024) for v, q, s in zip(views, qs, ss)]
+        offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+        pool = getattr(self, "_jpeg_out", None)
+        if pool is None or pool.size < int(offs[-1]):  # kept: fresh pages are the cost of a large buffer
+            pool = self._jpeg_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
+        base = pool.ctypes.data
+        rc, status, lens = self._jpeg_encode_call(views, qs, ss, [base + int(o) for o in offs[:-1]], caps)
+        if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL) and not (rc == L.FI_ENOMEM and rc in status):
+            L.check(rc)  # a failure of the call, not of an image
+        files = [pool[int(offs[i]):int(offs[i]) + lens[i]].tobytes() if status[i] == L.FI_OK else None for i in range(n)]
+        again = [i for i in range(n) if status[i] == L.FI_ENOMEM and lens[i] > caps[i]]
+        if again:
+            big = [np.empty(lens[i], np.uint8) for i in again]
+            rc, st2, len2 = self._jpeg_encode_call([views[i] for i in again], [qs[i] for i in again],
+                                                   [ss[i] for i in again], [b.ctypes.data for b in big],
+                                                   [lens[i] for i in again])
+            L.check(rc)
+            for k, i in enumerate(again):
+                files[i] = big[k][:len2[k]].tobytes()
+        return files
+
+    def jpeg_encode_host(self, images: list[np.ndarray], quality, subsampling) -> list[bytes | None]:
+        """jpeg_encode of host arrays (HW, HWC with 1..4 channels), uploaded to
+        scratch device buffers first (tests / tools): the counterpart of
+        jpeg_decode_host."""
+        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        ptrs = [self.malloc(max(a.nbytes, 1)) for a in arrs]
+        try:
+            views = []
+            for a, p in zip(arrs, ptrs):
+                self.h2d(p, a)
+                c = a.shape[2] if a.ndim == 3 else 1
+                views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
+            return self.jpeg_encode(views, quality, subsampling)
+        finally:
+            for p in ptrs:
+                self.free(p)
+
+    def process_device_resident(self, views, ops: list[Op]):
         """fi_process_batch_device on device-resident RGB8 sources given as
         (device pointer, width, height, stride) views (e.g. fi_jpeg_decode_device
-        targets, extract offsets applied); outputs land in a scratch device
-        buffer and come back as host arrays: (outputs, fi_image records, rc)
-        like ``process``."""
+        targets, extract offsets applied), the outputs left on the device (for
+        jpeg_encode): (base, out_views, fi_image records, rc); out_views[i] is
+        the (device pointer, w, h, stride, channels) view of output i or None,
+        inside the allocation ``base``, which the caller frees."""
         n = len(views)
         arr = (L.FiImage * max(n, 1))()
         for i, ((p, w, h, st), op) in enumerate(zip(views, ops)):
@@ -319,19 +417,29 @@ class Context:
             for i in range(n):
                 arr[i].dst, arr[i].dst_capacity = base + int(offs[i]), caps[i]
             rc = self._lib.fi_process_batch_device(self.h, arr, n)
+        except BaseException:
+            self.free(base)
+            raise
+        out_views = [(base + int(offs[i]), arr[i].out_w, arr[i].out_h, arr[i].out_stride, arr[i].out_channels)
+                     if arr[i].status == L.FI_OK else None for i in range(n)]
+        return base, out_views, [arr[i] for i in range(n)], rc
+
+    def process_device_views(self, views, ops: list[Op]):
+        """process_device_resident with the outputs copied back as host
+        arrays: (outputs, fi_image records, rc) like ``process``."""
+        base, out_views, recs, rc = self.process_device_resident(views, ops)
+        try:
             results = []
-            for i in range(n):
-                a = arr[i]
-                if a.status == L.FI_OK:
-                    o = self.d2h(base + int(offs[i]), a.out_h * a.out_stride)
-                    o = o.reshape(a.out_h, a.out_stride)[:, : a.out_w * a.out_channels]
-                    o = o.reshape(a.out_h, a.out_w, a.out_channels)
-                    results.append(o[:, :, 0] if a.out_channels == 1 else o)
-                else:
+            for v in out_views:
+                if v is None:
                     results.append(None)
+                    continue
+                p, w, h, st, c = v
+                o = self.d2h(p, h * st).reshape(h, st)[:, : w * c].reshape(h, w, c)
+                results.append(o[:, :, 0] if c == 1 else o)
         finally:
             self.free(base)
-        return results, [arr[i] for i in range(n)], rc
+        return results, recs, rc
 
     def fill_synthetic(self, dptr: int, w: int, h: int, stride: int, seed: int):
         L.check(self._lib.fi_fill_synthetic(self.h, dptr, w, h, stride, seed & 0xFFFFFFFF))

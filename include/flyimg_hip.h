@@ -214,8 +214,8 @@ int fi_process_batch_device(fi_ctx *ctx, fi_image *imgs, int32_t n);
  * k's records and outputs are final once that apply is done (fi_wait covers it).
  * Ordering across the two streams is kept for the caller: a later batch whose
  * sources overlap an earlier batch's dst, and the device-ordered entry points
- * (fi_pixelate_regions_device, fi_jpeg_decode_device, fi_fill_synthetic) wait
- * for the applies still running.  The dst buffers of two in-flight batches
+ * (fi_pixelate_regions_device, fi_jpeg_decode_device, fi_jpeg_encode_device,
+ * fi_fill_synthetic) wait for the applies still running.  The dst buffers of two in-flight batches
  * must not overlap (sources may be shared).
  * fi_wait(ctx, keep) finalizes submitted batches in order -- fills their
  * result fields -- until at most `keep` remain in flight (0 = drain all) and
@@ -313,6 +313,32 @@ int fi_jpeg_info(const uint8_t *data, size_t len, int32_t *w, int32_t *h, int32_
 int fi_jpeg_decode_device(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
                           uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,
                           int32_t *status);
+/* GPU JPEG encode: the write step of `convert` (IM writes the output with
+ * libjpeg at -quality) on the device, so the outputs of a device batch leave
+ * it compressed.  Baseline, Annex K Huffman tables, one restart interval per
+ * MCU row; the file is byte-identical with libjpeg-turbo's for the same
+ * pixels and settings (Pillow: Image.save(buf, "JPEG", quality=q,
+ * subsampling=s, restart_marker_rows=1)), and any baseline decoder reads it.
+ * subsampling: 0 = 4:4:4, 2 = 4:2:0 (3-channel images; ignored for gray).
+ * fi_jpeg_encode_bound (host only): an upper bound of the encoded size of any
+ * w x h image with these settings -- header, worst-case Huffman codes, 0xFF
+ * stuffing, restart markers, EOI; a worst case, many times a typical file.
+ * fi_jpeg_encode_device: encodes n device-resident images src[i] (HWC u8
+ * rows, 1 or 3 channels, any src_stride[i] >= w * channels, no alignment
+ * assumed: fi_process_batch_device outputs go in as they are) into the host
+ * buffers out[i] of out_cap[i] bytes and waits; out_len[i] = the encoded
+ * size.  status[i]: FI_EUNSUPPORTED for 2 or 4 channels (alpha: write PNG) or
+ * another subsampling, FI_EINVAL for quality outside 1..100 or a side outside
+ * 1..65535, FI_ENOMEM when out_cap[i] < out_len[i] (nothing is written past
+ * out_cap[i]; out_len[i] is the size needed).  Returns the first failing
+ * status; the other images are encoded.  Kernel times: "k_jpeg_fdct",
+ * "k_jpeg_henc", "k_jpeg_pack" in fi_kernel_stats (fi_set_timing(1)). */
+int fi_jpeg_encode_bound(int32_t w, int32_t h, int32_t channels, int32_t quality, int32_t subsampling,
+                         size_t *bytes);
+int fi_jpeg_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                          const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
+                          const int32_t *subsampling, int32_t n, uint8_t *const *out, const size_t *out_cap,
+                          size_t *out_len, int32_t *status);
 
 /* Test hook (not a reference interface): the skin / saturation table k_sc_fz
  * reads (2^24 entries, index (r << 16) | (g << 8) | b, value skin | sat << 8)

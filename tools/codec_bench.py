@@ -6,7 +6,17 @@ pageable buffers, encode), then pipelined (CodecPipeline.process_batches:
 decode into pinned slots, fi_submit_batch, encode of batch k during batch
 k+1), then with the JPEGs decoded on the GPU (CodecPipeline gpu_decode).
 Prints one JSON line with the stage splits; gpu_path_share = host time
-blocked on the GPU path / wall."""
+blocked on the GPU path / wall.
+
+--gpu-encode adds the A/B of the encode stage: the gpu_decode pipeline with
+the outputs encoded by the host threads against the same pipeline with
+gpu_encode (fi_jpeg_encode_device), --reps alternating passes over the same
+batches after a warm-up pass of each: images/s and the host seconds in the
+encode stage (median, min, max over the passes), the bytes a batch's outputs
+are as pixels and as files (with gpu_encode the files are what crosses PCIe),
+the size of the restart-marker files against the host encoder's files of the
+same pixels, and -- from one more, event-timed pass -- the three encode
+kernels' fi_kernel_stats times."""
 import argparse
 import io
 import json
@@ -23,6 +33,8 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--options", default="w_500,smc_1,q_90")
+    ap.add_argument("--gpu-encode", action="store_true", help="A/B the encode stage: host threads against the GPU")
+    ap.add_argument("--reps", type=int, default=5, help="alternating passes per setting of the --gpu-encode A/B")
     a = ap.parse_args()
     import numpy as np
     from PIL import Image
@@ -95,10 +107,65 @@ def main():
     gdec = {"images": done, "images_per_s": round(done / el, 1),
             "input_mpix_per_s": round(done * 1920 * 1080 / 1e6 / el, 1), "wall_s": round(el, 3)}
     gpipe.close()
-    print(json.dumps({"batch": a.batch, "threads": a.threads, "options": a.options, "serial": serial,
-                      "pipelined": piped, "gpu_decode": gdec}))
+    res = {"batch": a.batch, "threads": a.threads, "options": a.options, "serial": serial,
+           "pipelined": piped, "gpu_decode": gdec}
+    if a.gpu_encode:
+        res["gpu_encode_ab"] = encode_ab(ctx, codec, blobs, a)
+    print(json.dumps(res))
     pipe.close()
     ctx.close()
+
+
+def encode_ab(ctx, codec, blobs, a):
+    import statistics
+
+    def spread(v):
+        return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+
+    def one_pass(pipe):
+        pipe.process_stats = {"s_encode": 0.0, "raw_bytes": 0, "encoded_bytes": 0}
+        t0 = time.perf_counter()
+        done, files = 0, None
+        while done < a.images:
+            n = min(a.batch, a.images - done)
+            files, _ = pipe.process([blobs[(done + k) % len(blobs)] for k in range(n)], [a.options] * n)
+            done += n
+        return done / (time.perf_counter() - t0), dict(pipe.process_stats), files
+
+    pipes = {"host": codec.CodecPipeline(ctx, a.threads, gpu_decode=True),
+             "gpu": codec.CodecPipeline(ctx, a.threads, gpu_decode=True, gpu_encode=True)}
+    runs = {k: [] for k in pipes}
+    last = {}
+    for k, p in pipes.items():  # warm-up: every shape, every scratch buffer at its size
+        one_pass(p)
+    for _ in range(a.reps):
+        for k, p in pipes.items():
+            ips, st, last[k] = one_pass(p)
+            runs[k].append((ips, st))
+    out = {"images": a.images, "reps": a.reps}
+    nb = (a.images + a.batch - 1) // a.batch
+    for k in pipes:
+        st = runs[k][-1][1]
+        out[k + "_encode"] = {"images_per_s": spread([r[0] for r in runs[k]]),
+                              "s_encode": spread([r[1]["s_encode"] for r in runs[k]]),
+                              "raw_bytes_per_batch": st["raw_bytes"] // nb,
+                              "file_bytes_per_batch": st["encoded_bytes"] // nb}
+    out["d2h_bytes_per_batch"] = {"host_encode_pixels": out["host_encode"]["raw_bytes_per_batch"],
+                                  "gpu_encode_files": out["gpu_encode"]["file_bytes_per_batch"]}
+    # same pixels, same tables: what one restart interval per MCU row costs in bytes
+    out["restart_rows_size_ratio"] = round(sum(map(len, last["gpu"])) / sum(map(len, last["host"])), 4)
+    ctx.set_timing(1)
+    ctx.reset_stats()
+    one_pass(pipes["gpu"])
+    out["kernel_ms_per_pass"] = {}
+    for name in ("k_jpeg_fdct", "k_jpeg_henc", "k_jpeg_pack"):
+        ms, launches, _ = ctx.stats(name)
+        out["kernel_ms_per_pass"][name] = {"ms": round(ms, 3), "launches": launches}
+    ctx.set_timing(0)
+    ctx.reset_stats()
+    for p in pipes.values():
+        p.close()
+    return out
 
 
 if __name__ == "__main__":
