@@ -21,6 +21,7 @@ FI_ENOMEM = -3
 FI_EDEVICE = -4
 FI_EUNSUPPORTED = -5
 FI_ECAPACITY = -6
+FI_JPEG_PROGRESSIVE = 1  # fi_jpeg_info_ex / fi_jpeg_decode_device_ex flags
 
 FI_OP_THUMBNAIL = 1 << 0
 FI_OP_RESIZE = 1 << 1
@@ -193,6 +194,11 @@ def lib():
     L.fi_debug_host_plan.argtypes = [ctypes.POINTER(FiImage), i32, i32, ctypes.POINTER(ctypes.c_double)]
     L.fi_jpeg_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(i32), P(i32), P(i32)]
     L.fi_jpeg_decode_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp]
+    L.fi_jpeg_info_ex.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, P(i32), P(i32), P(i32), P(i32),
+                                  P(i32)]
+    L.fi_jpeg_decode_device_ex.argtypes = [vp, vp, vp, i32, vp, vp, i32, ctypes.c_uint32, vp]
+    L.fi_debug_jpeg_coefs_host.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, vp, vp, vp,
+                                           ctypes.c_size_t]
     L.fi_jpeg_encode_bound.argtypes = [i32, i32, i32, i32, i32, P(ctypes.c_size_t)]
     L.fi_jpeg_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     _lib = L

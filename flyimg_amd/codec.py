@@ -110,17 +110,19 @@ class _PinnedSlot:
         return self._slices(buf, sizes)
 
 
-def gpu_decodable(blob: bytes):
+def gpu_decodable(blob: bytes, progressive: bool = False):
     """(width, height, source channels) when the GPU decoder
     (fi_jpeg_decode_device, RGB output) produces exactly what decode_ex would:
     a baseline gray or YCbCr JPEG (fi_jpeg_info) with no EXIF rotation to
     apply; None otherwise (progressive, CMYK, PNG, ...).  A gray (1-component)
-    JPEG is an IM PseudoClass source, as decode_ex flags it."""
+    JPEG is an IM PseudoClass source, as decode_ex flags it.  With
+    ``progressive`` complete Huffman progressive JPEGs qualify as well
+    (fi_jpeg_info_ex / fi_jpeg_decode_device_ex, FI_JPEG_PROGRESSIVE)."""
     from PIL import Image
 
     from .runtime import jpeg_info
 
-    info = jpeg_info(blob)
+    info = jpeg_info(blob, progressive)
     if not info:
         return None
     try:
@@ -138,13 +140,21 @@ class CodecPipeline:
     default: the files carry restart markers, so their bytes differ from the
     host encoder's, the decoded pixels do not) ``process`` keeps the outputs
     on the device and writes every JPEG there with one fi_jpeg_encode_device
-    call; outputs with alpha still go through the host PNG writer."""
+    call; outputs with alpha still go through the host PNG writer.  With
+    ``gpu_progressive`` (off by default) progressive JPEG sources join the GPU
+    decode batch instead of the host threads (same pixels).  A progressive
+    scan is one serial chain on the GPU: measured on 1080p sources the GPU
+    path loses to 16 host threads below about 220 images per batch (172
+    against 403 img/s at batches of 64) and wins above (1956 against 652
+    img/s at 1024 images); DESIGN.md 3.5."""
 
-    def __init__(self, ctx, threads: int = 16, gpu_decode: bool = True, gpu_encode: bool = False):
+    def __init__(self, ctx, threads: int = 16, gpu_decode: bool = True, gpu_encode: bool = False,
+                 gpu_progressive: bool = False):
         self.ctx = ctx
         self.pool = ThreadPoolExecutor(max_workers=max(1, threads))
         self.gpu_decode = gpu_decode
         self.gpu_encode = gpu_encode
+        self.gpu_progressive = gpu_progressive
         # ``process``: host seconds in the encode stage, the bytes its outputs
         # were as pixels and are as files (with gpu_encode, what crosses PCIe)
         self.process_stats = {"s_encode": 0.0, "raw_bytes": 0, "encoded_bytes": 0}
@@ -183,7 +193,7 @@ class CodecPipeline:
         base = self.ctx.malloc(int(offs[-1]))
         try:
             ptrs = [base + int(o) for o in offs[:-1]]
-            status = self.ctx.jpeg_decode(blobs, ptrs, strides, channels=3)
+            status = self.ctx.jpeg_decode(blobs, ptrs, strides, channels=3, progressive=self.gpu_progressive)
             views, ops, keep = [], [], []
             for i, (bag, (w, h, c), p, st) in enumerate(zip(bags, dims, ptrs, strides)):
                 if status[i] != L.FI_OK:
@@ -254,7 +264,7 @@ class CodecPipeline:
         # extract (e_1) views start at any byte: the host path copies them to an
         # aligned array, so they decode there and take the same kernels
         # (bag.get: extract_key would consume the option, as InputImage::extractKey does)
-        dims = [gpu_decodable(b) if self.gpu_decode and _empty(bag.get("extract")) else None
+        dims = [gpu_decodable(b, self.gpu_progressive) if self.gpu_decode and _empty(bag.get("extract")) else None
                 for b, bag in zip(blobs, bags)]
         host = [i for i in range(n) if dims[i] is None]
         gpu = [i for i in range(n) if dims[i] is not None]

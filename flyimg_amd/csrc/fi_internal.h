@@ -422,5 +422,18 @@ struct JpegDesc {        // one image of a decode batch
 struct JpegInterval {    // one restart interval: its MCUs and where its bits start
   int32_t img, mcu0, mcu1, byte0;
 };
+// Progressive streams (k_jpeg_prog): one work item per (image, scan, restart
+// interval).  A single-component scan walks the component's own block raster
+// (`mcux` blocks per row, one block per MCU); an interleaved DC scan walks the
+// image's MCU grid.  Blocks are stored at row * bw + col of the padded grid.
+struct JpegProgItem {
+  int32_t img, level;      // descriptor index; launch level (scans of one level are independent)
+  int32_t ns, ci[3];       // components of the scan
+  int32_t tab[3];          // batch Huffman table per scan component (DC first), tab[0] for an AC scan; -1: none
+  int32_t Ss, Se, Ah, Al;
+  int32_t byte0, end;      // the interval's first byte and the scan's end, offsets in the image's segment
+  int32_t mcu0, mcu1;      // MCUs of this scan
+  int32_t mcux;            // MCUs per row of this scan
+};
 
 }  // namespace fi

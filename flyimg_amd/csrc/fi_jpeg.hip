@@ -20,6 +20,18 @@
 // Unsupported streams (progressive, arithmetic, 12-bit, CMYK / Adobe
 // transforms, other samplings, several scans) return FI_EUNSUPPORTED from
 // jpeg_parse so the caller decodes them on the host.
+//
+// Opt-in (FI_JPEG_PROGRESSIVE): complete Huffman progressive (SOF2) streams.
+//   host     every SOS up to EOI into a scan list (the tables and DRI in force
+//            at each), libjpeg's progression checks; each scan gets a level --
+//            1 + the highest level of an earlier scan sharing a component over
+//            an overlapping band -- and is cut into restart intervals;
+//   k_jpeg_prog   one launch per level, one 64-lane workgroup per (image,
+//            scan, restart interval): jdphuff.c's DC / AC first and refinement
+//            procedures (fi_jpeg_prog.h, shared with the host decoder of
+//            fi_jpeg_prog_host.cpp) into the zeroed coefficient planes;
+//   then the same k_jpeg_idct and k_jpeg_color launches as the baseline
+//   images of the batch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -33,6 +45,7 @@
 
 #include "fi_internal.h"
 #include "fi_jpeg.h"
+#include "fi_jpeg_prog.h"
 
 namespace fi {
 
@@ -239,6 +252,140 @@ __global__ __launch_bounds__(64) void k_jpeg_huff(const JpegDesc *__restrict__ d
           }
         }
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// device: progressive scans (jdphuff.c), one 64-lane workgroup per (image,
+// scan, restart interval) of one level
+// ---------------------------------------------------------------------------
+// The block procedures are fi_jpeg_prog.h's (shared with the host decoder),
+// over the lockstep BitReader.  Only the scan's own tables are staged in LDS
+// (one AC table, or up to three DC tables).  Lane z works on coefficient z: a
+// first-pass scan writes its band Ss .. Se of a staging block in LDS; a
+// refinement scan loads the band into registers (the next block's is in flight
+// while this one decodes) and runs on ballots of it.  Every scan stores its
+// band only, one 2-byte store per lane -- two scans of one level may share a
+// 128-byte block (Y 1-5 and Y 6-63).
+struct JpegProgDevOps {
+  template <typename TAB>
+  static __device__ __forceinline__ int sym(BitReader &br, const TAB *t) {
+    return jpeg_decode_sym(br, t);
+  }
+  // lane z looks up the bit of its own coefficient
+  static __device__ __forceinline__ uint64_t deposit(uint64_t bits, int n, uint64_t m) {
+    const int z = threadIdx.x & 63;
+    const bool in = (m >> z) & 1;
+    const int rank = __builtin_popcountll(m & (((uint64_t)1 << z) - 1));
+    return __ballot(in && ((bits >> (in ? n - 1 - rank : 0)) & 1));
+  }
+};
+
+__global__ __launch_bounds__(64) void k_jpeg_prog(const JpegDesc *__restrict__ descs,
+                                                  const JpegProgItem *__restrict__ items, int nitems,
+                                                  const JpegHuff *__restrict__ huff, uint8_t *__restrict__ work) {
+  __shared__ JpegHuff sh[3];
+  __shared__ __attribute__((aligned(16))) int16_t blk[64];
+  typedef __attribute__((address_space(3))) const JpegHuff l_huff;
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x >= nitems) return;
+  const JpegProgItem I = items[blockIdx.x];
+#pragma unroll
+  for (int t = 0; t < 3; t++) {
+    if (I.tab[t] < 0) continue;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(huff + I.tab[t]);
+    uint32_t *dstw = reinterpret_cast<uint32_t *>(sh + t);
+    for (int i = tid; i < (int)sizeof(JpegHuff) / 4; i += 64) dstw[i] = src[i];
+  }
+  blk[tid] = 0;
+  __syncthreads();
+  const JpegDesc *Dp = descs + I.img;
+  int hs[3], vs[3], bw[3];
+  int64_t co[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const bool on = k < I.ns;
+    const int c = on ? I.ci[k] : 0;
+    hs[k] = on && I.ns > 1 ? Dp->h[c] : 1;
+    vs[k] = on && I.ns > 1 ? Dp->v[c] : 1;
+    bw[k] = Dp->bw[c];
+    co[k] = Dp->coef[c];
+  }
+  const bool dc = I.Ss == 0, refine = I.Ah != 0;
+  const bool mine = tid >= I.Ss && tid <= I.Se;  // this lane's coefficient is in the scan's band
+  const int Ss = I.Ss, Se = I.Se, Al = I.Al;
+  // the scan's blocks in decode order: block j of the interval is sub-block
+  // j % bpm of MCU mcu0 + j / bpm (bpm = 1 for a single-component scan)
+  const int n0 = hs[0] * vs[0], n1 = I.ns > 1 ? hs[1] * vs[1] : 0, n2 = I.ns > 2 ? hs[2] * vs[2] : 0;
+  const int bpm = n0 + n1 + n2;
+  const int nblk = (I.mcu1 - I.mcu0) * bpm;
+  int16_t *const w16 = reinterpret_cast<int16_t *>(work);
+  // -> element offset of block j's coefficients; k = its component slot
+  auto locate = [&](int j, int &k) -> int64_t {
+    const int m = j / bpm;
+    int idx = j - m * bpm;
+    k = idx < n0 ? 0 : idx < n0 + n1 ? 1 : 2;
+    idx -= k == 0 ? 0 : k == 1 ? n0 : n0 + n1;
+    const int h = k == 0 ? hs[0] : k == 1 ? hs[1] : hs[2], v = k == 0 ? vs[0] : k == 1 ? vs[1] : vs[2];
+    const int by = idx / h, bx = idx - by * h;
+    const int64_t base = (k == 0 ? co[0] : k == 1 ? co[1] : co[2]) >> 1;
+    return base + jpeg_prog_block(I, I.mcu0 + m, h, v, by, bx, k == 0 ? bw[0] : k == 1 ? bw[1] : bw[2]) * 64;
+  };
+  BitReader br;
+  br.init(Dp->ecs, I.byte0, I.end);
+  JpegProgState S{};
+  int16_t *b = blk;
+  int k = 0;
+  if (!refine) {
+    // first pass: the procedure writes the band of the staging block (zero
+    // before), the band's lanes store it
+    for (int j = 0; j < nblk; j++) {
+      if (!dc && S.eobrun > 0) {  // the blocks of an end-of-band run stay zero
+        const uint32_t left = (uint32_t)(nblk - j), skip = S.eobrun < left ? S.eobrun : left;
+        S.eobrun -= skip;
+        j += (int)skip - 1;
+        continue;
+      }
+      int16_t *g = w16 + locate(j, k);
+      if (dc) {
+        if (k == 0)
+          jpeg_prog_dc_first<JpegProgDevOps>(br, (l_huff *)(sh + 0), b, S.pred[0], Al);
+        else if (k == 1)
+          jpeg_prog_dc_first<JpegProgDevOps>(br, (l_huff *)(sh + 1), b, S.pred[1], Al);
+        else
+          jpeg_prog_dc_first<JpegProgDevOps>(br, (l_huff *)(sh + 2), b, S.pred[2], Al);
+      } else {
+        jpeg_prog_ac_first<JpegProgDevOps>(br, (l_huff *)(sh + 0), b, S.eobrun, Ss, Se, Al);
+      }
+      if (mine) {
+        g[tid] = b[tid];
+        b[tid] = 0;
+      }
+    }
+    return;
+  }
+  // refinement: lane z holds coefficient z of the block (the next block's is
+  // in flight while this one decodes); the procedure works on ballots of them
+  int16_t pre = 0;
+  if (mine && nblk > 0) pre = w16[locate(0, k) + tid];
+  for (int j = 0; j < nblk; j++) {
+    int16_t *g = w16 + locate(j, k);
+    const int16_t cur = pre;
+    if (mine && j + 1 < nblk) {
+      int kn;
+      pre = w16[locate(j + 1, kn) + tid];
+    }
+    int16_t out;
+    if (dc) {
+      out = jpeg_prog_dc_refine(br) ? (int16_t)(cur | (1 << Al)) : cur;
+    } else {
+      JpegProgRefine R{};
+      R.nz = __ballot(mine && cur != 0);
+      R.has = __ballot(mine && (cur & (1 << Al)) != 0);
+      jpeg_prog_ac_refine<JpegProgDevOps>(br, (l_huff *)(sh + 0), R, S.eobrun, Ss, Se);
+      out = jpeg_prog_refined(cur, tid, R, Al);
+    }
+    if (mine && out != cur) g[tid] = out;
   }
 }
 
@@ -462,8 +609,9 @@ __global__ __launch_bounds__(256) void k_jpeg_color(const JpegDesc *__restrict__
 // stays valid until the stream has run: 0 device upload (compressed data +
 // tables), 2 device work (coefficients + planes), 3 pinned host staging.
 int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *len, int n, uint8_t *const *dst,
-                      const int64_t *dst_stride, int out_channels, int32_t *status,
-                      void *(*alloc)(void *, int, size_t), void *actx, std::string *err) {
+                      const int64_t *dst_stride, int out_channels, uint32_t flags, int32_t *status,
+                      void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *), void *actx,
+                      std::string *err) {
   std::vector<JpegHdr> hd(n);
   std::vector<int> ok(n, 0);
   std::map<std::string, int> huff_ix;
@@ -472,6 +620,9 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   std::vector<JpegDesc> descs;
   std::vector<int> desc_img;
   std::vector<JpegInterval> ivs;
+  std::vector<JpegProgItem> pitems;  // progressive streams: (image, scan, restart interval)
+  std::vector<char> desc_prog;
+  size_t pcoef_total = 0;            // their coefficient planes: one region at the end of the work buffer, zeroed
   std::vector<int64_t> blk0;  // first block of each (image, component)
   int64_t nblocks = 0;
   std::vector<int64_t> px0(1, 0);
@@ -492,7 +643,7 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
       });
     for (auto &t : th) t.join();
   };
-  parallel(n, [&](int i) { status[i] = jpeg_parse(data[i], len[i], &hd[i]); });
+  parallel(n, [&](int i) { status[i] = jpeg_parse(data[i], len[i], &hd[i], flags); });
   for (int i = 0; i < n; i++) {
     if (status[i]) continue;
     JpegHdr &H = hd[i];
@@ -505,6 +656,22 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
       D.hmax = std::max(D.hmax, H.h[c]);
       D.vmax = std::max(D.vmax, H.v[c]);
     }
+    // a progressive stream's tables: the ones its scans use, deduplicated over the batch as well
+    std::vector<int> tabmap(H.ptab.size());
+    for (size_t t = 0; t < H.ptab.size() && !status[i]; t++) {
+      auto it = huff_ix.find(H.ptab[t]);
+      if (it == huff_ix.end()) {
+        JpegHuff hf;
+        if (!jpeg_build_huff(H.ptab[t].substr(1), H.ptab[t][0] == 'D', &hf)) {
+          status[i] = FI_EINVAL;
+          break;
+        }
+        it = huff_ix.emplace(H.ptab[t], (int)huffs.size()).first;
+        huffs.push_back(hf);
+      }
+      tabmap[t] = it->second;
+    }
+    if (status[i]) continue;
     D.mcux = (H.W + 8 * D.hmax - 1) / (8 * D.hmax);
     D.mcuy = (H.H + 8 * D.vmax - 1) / (8 * D.vmax);
     D.qt = (int)(qts.size() / 64);
@@ -513,7 +680,7 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
     // tables are shared by all its images: a few distinct tables, LDS resident)
     for (int t = 0; t < 4; t++) {
       D.ht[t] = -1;
-      if (H.dht[t].empty()) continue;
+      if (H.dht[t].empty() || H.progressive) continue;
       const std::string key = std::string(1, t < 2 ? 'D' : 'A') + H.dht[t];  // class + table bytes
       auto it = huff_ix.find(key);
       if (it == huff_ix.end()) {
@@ -538,8 +705,13 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
       D.bh[c] = D.mcuy * H.v[c];
       D.dw[c] = (H.W * H.h[c] + D.hmax - 1) / D.hmax;  // jdmaster.c downsampled_width
       D.dh[c] = (H.H * H.v[c] + D.vmax - 1) / D.vmax;
-      D.coef[c] = (int64_t)work_total;
-      work_total += (size_t)D.bw[c] * D.bh[c] * 128;
+      if (H.progressive) {  // (offset in the zeroed region until placed)
+        D.coef[c] = (int64_t)pcoef_total;
+        pcoef_total += (size_t)D.bw[c] * D.bh[c] * 128;
+      } else {
+        D.coef[c] = (int64_t)work_total;
+        work_total += (size_t)D.bw[c] * D.bh[c] * 128;
+      }
       D.plane[c] = (int64_t)work_total;
       work_total += ((size_t)D.bw[c] * 8 * D.bh[c] * 8 + 255) & ~(size_t)255;
     }
@@ -551,7 +723,11 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
     const int img = (int)descs.size();
     // restart intervals: RSTn markers split the segment
     const int nmcu = D.mcux * D.mcuy;
-    if (H.restart > 0) {
+    if (H.progressive) {
+      JpegGeom G;
+      jpeg_geom(H, &G);
+      jpeg_prog_items(H, G, data[i], img, tabmap.data(), &pitems);
+    } else if (H.restart > 0) {
       const uint8_t *e = data[i] + H.ecs0;
       int byte0 = 0, mcu0 = 0;
       for (size_t q = 0; q + 1 < (size_t)D.ecs_len && mcu0 < nmcu; q++) {
@@ -571,11 +747,23 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
       if (c < H.ncomp) nblocks += (int64_t)D.bw[c] * D.bh[c];
     }
     px0.push_back(px0.back() + (int64_t)H.W * H.H);
-    ecs_total += ((size_t)D.ecs_len + 512 + 255) & ~(size_t)255;  // zero pad: the reader's window
+    // zero pad: the reader's window (a progressive scan's reader stops at its scan's end, inside the segment)
+    ecs_total += ((size_t)D.ecs_len + 512 + 255) & ~(size_t)255;
     descs.push_back(D);
+    desc_prog.push_back(H.progressive);
     desc_img.push_back(i);
   }
   if (descs.empty()) return 0;
+  // the progressive images' coefficients: after everything else
+  work_total = (work_total + 255) & ~(size_t)255;
+  for (size_t k = 0; k < descs.size(); k++)
+    if (desc_prog[k])
+      for (int c = 0; c < descs[k].ncomp; c++) descs[k].coef[c] += (int64_t)work_total;
+  const size_t pcoef0 = work_total;
+  work_total += pcoef_total;
+  // scans of one level are independent: one launch per level, in order
+  std::stable_sort(pitems.begin(), pitems.end(),
+                   [](const JpegProgItem &a, const JpegProgItem &b) { return a.level < b.level; });
   // one upload: compressed data (each segment zero padded for the reader's
   // window) then tables + descriptors, staged in pinned host memory
   const size_t o_desc = 0, o_iv = o_desc + ((descs.size() * sizeof(JpegDesc) + 255) & ~(size_t)255);
@@ -584,7 +772,8 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   const size_t o_huff = o_ref + ((blk0.size() * 8 + 255) & ~(size_t)255);
   const size_t o_qt = o_huff + ((huffs.size() * sizeof(JpegHuff) + 255) & ~(size_t)255);
   const size_t o_px = o_qt + ((qts.size() * 2 + 255) & ~(size_t)255);
-  const size_t tab0 = (ecs_total + 255) & ~(size_t)255, up_total = tab0 + o_px + px0.size() * 8;
+  const size_t o_pit = o_px + ((px0.size() * 8 + 255) & ~(size_t)255);
+  const size_t tab0 = (ecs_total + 255) & ~(size_t)255, up_total = tab0 + o_pit + pitems.size() * sizeof(JpegProgItem);
   uint8_t *din = (uint8_t *)alloc(actx, 0, up_total);
   uint8_t *hst = (uint8_t *)alloc(actx, 3, up_total);
   uint8_t *dwork = (uint8_t *)alloc(actx, 2, std::max(work_total, (size_t)256));
@@ -608,6 +797,7 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   memcpy(htab + o_huff, huffs.data(), huffs.size() * sizeof(JpegHuff));
   memcpy(htab + o_qt, qts.data(), qts.size() * 2);
   memcpy(htab + o_px, px0.data(), px0.size() * 8);
+  if (!pitems.empty()) memcpy(htab + o_pit, pitems.data(), pitems.size() * sizeof(JpegProgItem));
   if (hipMemcpyAsync(din, hst, up_total, hipMemcpyHostToDevice, st) != hipSuccess) {
     *err = "JPEG batch upload";
     return FI_EDEVICE;
@@ -616,12 +806,30 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   // the distinct Huffman tables go to LDS when they are few (kJpegLdsTabs)
   const int nhuff = (int)huffs.size();
   const dim3 g((unsigned)ivs.size());  // one restart interval per 64-lane workgroup
-  if (nhuff <= kJpegLdsTabs)
+  if (ivs.empty()) {
+    // (progressive streams only)
+  } else if (nhuff <= kJpegLdsTabs)
     hipLaunchKernelGGL(k_jpeg_huff<true>, g, dim3(64), 0, st, dd, (const JpegInterval *)(dtab + o_iv), (int)ivs.size(),
                        (const JpegHuff *)(dtab + o_huff), nhuff, dwork);
   else
     hipLaunchKernelGGL(k_jpeg_huff<false>, g, dim3(64), 0, st, dd, (const JpegInterval *)(dtab + o_iv),
                        (int)ivs.size(), (const JpegHuff *)(dtab + o_huff), nhuff, dwork);
+  if (!pitems.empty()) {
+    if (hipMemsetAsync(dwork + pcoef0, 0, pcoef_total, st) != hipSuccess) {
+      *err = "JPEG coefficient clear";
+      return FI_EDEVICE;
+    }
+    if (stage) stage(actx, "k_jpeg_prog");
+    for (size_t a = 0; a < pitems.size();) {
+      size_t z = a;
+      while (z < pitems.size() && pitems[z].level == pitems[a].level) z++;
+      hipLaunchKernelGGL(k_jpeg_prog, dim3((unsigned)(z - a)), dim3(64), 0, st, dd,
+                         (const JpegProgItem *)(dtab + o_pit) + a, (int)(z - a), (const JpegHuff *)(dtab + o_huff),
+                         dwork);
+      a = z;
+    }
+    if (stage) stage(actx, nullptr);
+  }
   hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)std::min<int64_t>((nblocks + 255) / 256, 1 << 20)), dim3(256), 0, st, dd,
                      (const int64_t *)(dtab + o_ref), (int)descs.size(), (const uint16_t *)(dtab + o_qt), dwork);
   hipLaunchKernelGGL(k_jpeg_color, dim3((unsigned)std::min<int64_t>((px0.back() + 255) / 256, 1 << 20)), dim3(256), 0, st, dd,

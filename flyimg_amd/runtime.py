@@ -67,12 +67,54 @@ def plan_bytes(sizes_ops):
     return [int(out[i]) for i in range(n)]
 
 
-def jpeg_info(blob: bytes):
+def jpeg_info(blob: bytes, progressive: bool = False):
     """(width, height, channels) of a JPEG the GPU decoder handles, else None
-    (fi_jpeg_info: progressive, CMYK, 4:1:1, ... decode on the host)."""
+    (fi_jpeg_info: progressive, CMYK, 4:1:1, ... decode on the host).
+    ``progressive=True`` (fi_jpeg_info_ex, FI_JPEG_PROGRESSIVE) also takes
+    complete Huffman progressive streams."""
     w, h, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-    rc = L.lib().fi_jpeg_info(blob, len(blob), ctypes.byref(w), ctypes.byref(h), ctypes.byref(c))
+    if progressive:
+        rc = L.lib().fi_jpeg_info_ex(blob, len(blob), L.FI_JPEG_PROGRESSIVE, ctypes.byref(w), ctypes.byref(h),
+                                     ctypes.byref(c), None, None)
+    else:
+        rc = L.lib().fi_jpeg_info(blob, len(blob), ctypes.byref(w), ctypes.byref(h), ctypes.byref(c))
     return (w.value, h.value, c.value) if rc == L.FI_OK else None
+
+
+def jpeg_scan_info(blob: bytes):
+    """(width, height, channels, nscans, nlevels) of a JPEG the GPU decoder
+    handles with FI_JPEG_PROGRESSIVE (fi_jpeg_info_ex: a baseline stream is one
+    scan in one level; a progressive stream's scans run in ``nlevels``
+    launches), else None.  ``jpeg_scan_status`` tells invalid from unsupported."""
+    return jpeg_scan_status(blob)[1]
+
+
+def jpeg_scan_status(blob: bytes):
+    """(status, info): fi_jpeg_info_ex's return code under FI_JPEG_PROGRESSIVE
+    (0, FI_EUNSUPPORTED: decode on the host, FI_EINVAL: malformed) and
+    jpeg_scan_info's tuple (None unless the status is 0)."""
+    v = [ctypes.c_int32() for _ in range(5)]
+    rc = L.lib().fi_jpeg_info_ex(blob, len(blob), L.FI_JPEG_PROGRESSIVE, *[ctypes.byref(x) for x in v])
+    return rc, (tuple(x.value for x in v) if rc == L.FI_OK else None)
+
+
+def jpeg_coefs_host(blob: bytes, progressive: bool = True):
+    """fi_debug_jpeg_coefs_host (test hook): a progressive stream's entropy
+    decode on the CPU -- ([int16 (bh, bw, 64) zigzag blocks per component],
+    [uint16 (64,) natural-order quant table per component]), or None."""
+    flags = L.FI_JPEG_PROGRESSIVE if progressive else 0
+    info = (ctypes.c_int32 * 7)()
+    qt = np.zeros(192, np.uint16)
+    fn = L.lib().fi_debug_jpeg_coefs_host
+    if fn(blob, len(blob), flags, info, qt.ctypes.data, None, 0) != L.FI_OK:
+        return None
+    n = info[0]
+    sizes = [info[1 + k] * info[4 + k] * 64 for k in range(3)]
+    co = np.zeros(sum(sizes), np.int16)
+    L.check(fn(blob, len(blob), flags, info, qt.ctypes.data, co.ctypes.data, co.size))
+    offs = np.cumsum([0] + sizes)
+    return ([co[offs[k]:offs[k + 1]].reshape(info[4 + k], info[1 + k], 64) for k in range(n)],
+            [qt[64 * k:64 * k + 64] for k in range(n)])
 
 
 def jpeg_encode_bound(w: int, h: int, channels: int, quality: int, subsampling: int = 0) -> int:
@@ -268,8 +310,10 @@ class Context:
         L.check(self._lib.fi_memcpy_d2h(self.h, out.ctypes.data, dptr, nbytes))
         return out
 
-    def jpeg_decode(self, blobs: list[bytes], dptrs: list[int], strides: list[int], channels: int = 0) -> list[int]:
-        """fi_jpeg_decode_device: decodes baseline JPEG byte strings into the
+    def jpeg_decode(self, blobs: list[bytes], dptrs: list[int], strides: list[int], channels: int = 0,
+                    progressive: bool = False) -> list[int]:
+        """fi_jpeg_decode_device: decodes baseline JPEG byte strings (with
+        ``progressive=True``, fi_jpeg_decode_device_ex: progressive ones too) into the
         device buffers ``dptrs`` (HWC rows of ``strides`` bytes; channels as
         jpeg_info says, or 3 for every image with ``channels=3``: gray
         replicated); returns the per-image status (0 = decoded,
@@ -281,20 +325,24 @@ class Context:
         dst = (ctypes.c_void_p * n)(*dptrs)
         st = (ctypes.c_int64 * n)(*strides)
         status = (ctypes.c_int32 * n)()
-        rc = self._lib.fi_jpeg_decode_device(self.h, data, lens, n, dst, st, channels, status)
+        if progressive:
+            rc = self._lib.fi_jpeg_decode_device_ex(self.h, data, lens, n, dst, st, channels, L.FI_JPEG_PROGRESSIVE,
+                                                    status)
+        else:
+            rc = self._lib.fi_jpeg_decode_device(self.h, data, lens, n, dst, st, channels, status)
         if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL):
             L.check(rc)
         return list(status)
 
-    def jpeg_decode_host(self, blobs: list[bytes]) -> list[np.ndarray | None]:
+    def jpeg_decode_host(self, blobs: list[bytes], progressive: bool = False) -> list[np.ndarray | None]:
         """jpeg_decode into scratch device buffers, copied back (tests / tools):
         HWC uint8 arrays (H, W, 3) or (H, W) for gray; None where the GPU
         decoder returned a non-zero status."""
-        infos = [jpeg_info(b) for b in blobs]
+        infos = [jpeg_info(b, progressive) for b in blobs]
         sizes = [(i[0] * i[1] * i[2]) if i else 1 for i in infos]
         ptrs = [self.malloc(max(sz, 1)) for sz in sizes]
         try:
-            status = self.jpeg_decode(blobs, ptrs, [(i[0] * i[2]) if i else 1 for i in infos])
+            status = self.jpeg_decode(blobs, ptrs, [(i[0] * i[2]) if i else 1 for i in infos], progressive=progressive)
             out = []
             for info, p, sz, s in zip(infos, ptrs, sizes, status):
                 if s != 0 or not info:

@@ -313,6 +313,36 @@ int fi_jpeg_info(const uint8_t *data, size_t len, int32_t *w, int32_t *h, int32_
 int fi_jpeg_decode_device(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
                           uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,
                           int32_t *status);
+/* Progressive sources, opt-in: with FI_JPEG_PROGRESSIVE in `flags` the two
+ * functions below also take SOF2 (Huffman progressive, 8-bit) streams of the
+ * same colour spaces and samplings, provided the scan script is complete --
+ * every coefficient of every component sent and refined to its last bit, as
+ * every encoder's output is; an incomplete file (libjpeg smooths its blocks),
+ * a scan script libjpeg would warn about, more than 64 scans, or data after
+ * EOI is FI_EUNSUPPORTED, and a scan libjpeg rejects (JERR_BAD_PROGRESSION)
+ * FI_EINVAL.  The pixels are libjpeg-turbo's, bit for bit.  With flags 0 both
+ * are fi_jpeg_info / fi_jpeg_decode_device.
+ * fi_jpeg_info_ex (host only): also the stream's scan count and the number of
+ * launch levels its scans are scheduled in (scans that share no component
+ * over overlapping coefficient bands run in one launch); 1 and 1 for a
+ * baseline stream; nscans / nlevels may be NULL.
+ * fi_jpeg_decode_device_ex: a batch may mix baseline and progressive streams
+ * (one upload, one IDCT and one colour launch for all).  Kernel time of the
+ * progressive entropy decode: "k_jpeg_prog" in fi_kernel_stats
+ * (fi_set_timing(1)). */
+#define FI_JPEG_PROGRESSIVE 1u   /* also take SOF2 Huffman progressive streams */
+int fi_jpeg_info_ex(const uint8_t *data, size_t len, uint32_t flags, int32_t *w, int32_t *h, int32_t *channels,
+                    int32_t *nscans, int32_t *nlevels);
+int fi_jpeg_decode_device_ex(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
+                             uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,
+                             uint32_t flags, int32_t *status);
+/* Test hook (not a reference interface): the progressive entropy decode on
+ * the CPU, through the block procedures the device kernel runs: info =
+ * {components, bw[3], bh[3]} (block grid of each component), qt = each
+ * component's quantisation table (natural order), coefs (NULL: sizes only) =
+ * the int16 blocks in zigzag order, component after component. */
+int fi_debug_jpeg_coefs_host(const uint8_t *data, size_t len, uint32_t flags, int32_t info[7], uint16_t qt[192],
+                             int16_t *coefs, size_t coefs_cap);
 /* GPU JPEG encode: the write step of `convert` (IM writes the output with
  * libjpeg at -quality) on the device, so the outputs of a device batch leave
  * it compressed.  Baseline, Annex K Huffman tables, one restart interval per

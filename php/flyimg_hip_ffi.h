@@ -50,3 +50,8 @@ void fi_smartcrop_default_params(fi_smartcrop_params *p);
 int fi_smartcrop(fi_ctx *ctx, const uint8_t *rgb, int32_t w, int32_t h, int32_t stride,
                  int32_t target_w, int32_t target_h, const fi_smartcrop_params *params,
                  int32_t out_xywh[4], double *out_score);
+int fi_jpeg_info_ex(const uint8_t *data, size_t len, uint32_t flags, int32_t *w, int32_t *h, int32_t *channels,
+                    int32_t *nscans, int32_t *nlevels);
+int fi_jpeg_decode_device_ex(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
+                             uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,
+                             uint32_t flags, int32_t *status);

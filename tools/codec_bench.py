@@ -35,7 +35,11 @@ def main():
     ap.add_argument("--options", default="w_500,smc_1,q_90")
     ap.add_argument("--gpu-encode", action="store_true", help="A/B the encode stage: host threads against the GPU")
     ap.add_argument("--reps", type=int, default=5, help="alternating passes per setting of the --gpu-encode A/B")
+    ap.add_argument("--progressive", action="store_true",
+                    help="only the A/B of CodecPipeline(gpu_progressive=...) on progressive sources")
     a = ap.parse_args()
+    if a.progressive:
+        return progressive_ab(a)
     import numpy as np
     from PIL import Image
 
@@ -113,6 +117,53 @@ def main():
         res["gpu_encode_ab"] = encode_ab(ctx, codec, blobs, a)
     print(json.dumps(res))
     pipe.close()
+    ctx.close()
+
+
+def progressive_ab(a):
+    """Progressive 1080p sources through CodecPipeline.process with the
+    gpu_progressive switch off (16 host threads decode them) and on (they join
+    the GPU decode batch): alternating passes, images/s of each."""
+    import statistics
+
+    from PIL import Image
+
+    from flyimg_amd import codec
+    from flyimg_amd.runtime import Context
+    from flyimg_amd.synth import synth_rgb
+
+    blobs = []
+    for i in range(8):
+        b = io.BytesIO()
+        Image.fromarray(synth_rgb(1920, 1080, 100 + i)).save(b, "JPEG", quality=90, subsampling=2, progressive=True)
+        blobs.append(b.getvalue())
+    ctx = Context(0)
+    pipes = {"off": codec.CodecPipeline(ctx, a.threads), "on": codec.CodecPipeline(ctx, a.threads, gpu_progressive=True)}
+
+    def one_pass(pipe):
+        t0 = time.perf_counter()
+        done, files = 0, None
+        while done < a.images:
+            n = min(a.batch, a.images - done)
+            files, _ = pipe.process([blobs[(done + k) % len(blobs)] for k in range(n)], [a.options] * n)
+            done += n
+        return done / (time.perf_counter() - t0), files
+
+    last, runs = {}, {k: [] for k in pipes}
+    for p in pipes.values():
+        one_pass(p)  # warm-up
+    for _ in range(a.reps):
+        for k, p in pipes.items():
+            ips, last[k] = one_pass(p)
+            runs[k].append(ips)
+    res = {"images": a.images, "batch": a.batch, "threads": a.threads, "options": a.options, "reps": a.reps,
+           "sources": "1920x1080 q90 4:2:0 progressive (Pillow)", "same_output_bytes": last["on"] == last["off"]}
+    for k, v in runs.items():
+        res["gpu_progressive_" + k] = {"images_per_s": {"median": round(statistics.median(v), 1),
+                                                        "min": round(min(v), 1), "max": round(max(v), 1)}}
+    print(json.dumps(res))
+    for p in pipes.values():
+        p.close()
     ctx.close()
 
 
