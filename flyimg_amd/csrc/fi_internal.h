@@ -1,5 +1,5 @@
 // fi_internal.h -- structures shared by the host planner (fi_plan.cpp), the
-// runtime (fi_api.cpp) and the gfx950 kernels (fi_kernels.hip).
+// runtime (fi_runtime.h and its files) and the gfx950 kernels (fi_kernels.hip).
 //
 // Data layout in HBM (see DESIGN.md "Data layout"):
 //   * images: RGB8 HWC rows, caller stride;

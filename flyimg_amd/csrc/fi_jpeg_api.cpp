@@ -1,0 +1,134 @@
+// fi_jpeg_api.cpp -- the GPU JPEG decode / encode entry points of the runtime
+// (fi_runtime.h; the codecs are fi_jpeg.hip, fi_jpeg_enc.hip and their host parsers).
+#include "fi_runtime.h"
+#include "fi_jpeg.h"
+#include "fi_jpeg_enc.h"
+
+using namespace fi;
+
+extern "C" {
+
+// GPU JPEG decode (fi_jpeg.hip): the decode half of the host codec pipeline
+// (ImageProcessor's `convert` reads the source with libjpeg) on the device
+int fi_jpeg_info_ex(const uint8_t *data, size_t len, uint32_t flags, int32_t *w, int32_t *h, int32_t *channels,
+                    int32_t *nscans, int32_t *nlevels) {
+  if (!data || !w || !h || !channels || (flags & ~FI_JPEG_PROGRESSIVE)) return set_err(FI_EINVAL, "bad arguments");
+  int W = 0, H = 0, C = 0, NS = 0, NL = 0;
+  const int rc = jpeg_info_ex(data, len, flags, &W, &H, &C, &NS, &NL);
+  if (rc) return set_err(rc, rc == FI_EUNSUPPORTED ? "JPEG stream the GPU decoder does not handle" : "malformed JPEG");
+  *w = W;
+  *h = H;
+  *channels = C;
+  if (nscans) *nscans = NS;
+  if (nlevels) *nlevels = NL;
+  return FI_OK;
+}
+int fi_jpeg_info(const uint8_t *data, size_t len, int32_t *w, int32_t *h, int32_t *channels) {
+  return fi_jpeg_info_ex(data, len, 0, w, h, channels, nullptr, nullptr);
+}
+static void *jpeg_alloc(void *actx, int which, size_t bytes) {
+  fi_ctx *c = static_cast<fi_ctx *>(actx);
+  if (which == 3)  // pinned host staging (the previous call has synchronised)
+    return ensure_pinned_buf(&c->jpeg_host, &c->jpeg_host_cap, bytes) == FI_OK ? c->jpeg_host : nullptr;
+  return ensure(c, &c->jpeg[which], bytes) == FI_OK ? c->jpeg[which].p : nullptr;
+}
+static void jpeg_enc_stage(void *actx, const char *name);
+int fi_jpeg_decode_device_ex(fi_ctx *c, const uint8_t *const *data, const size_t *len, int32_t n, uint8_t *const *dst,
+                             const int64_t *dst_stride, int32_t out_channels, uint32_t flags, int32_t *status) {
+  if (!c || n < 0 || (n > 0 && (!data || !len || !dst || !dst_stride || !status)) ||
+      (out_channels != 0 && out_channels != 3) || (flags & ~FI_JPEG_PROGRESSIVE))
+    return set_err(FI_EINVAL, "bad arguments");
+  if (n == 0) return FI_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
+  std::string err;
+  // (the stage callback times k_jpeg_prog the way the encode kernels are timed)
+  const int rc = jpeg_decode_batch(c->stream, data, len, n, dst, dst_stride, out_channels, flags, status, jpeg_alloc,
+                                   jpeg_enc_stage, c, &err);
+  jpeg_enc_stage(c, nullptr);
+  collect_timers(c);
+  if (rc) return set_err(rc, "%s", err.c_str());
+  for (int i = 0; i < n; i++)  // the others are decoded; the caller decodes these on the host
+    if (status[i])
+      return set_err(status[i], "image %d: %s", i,
+                     status[i] == FI_EUNSUPPORTED ? "JPEG stream the GPU decoder does not handle" : "malformed JPEG");
+  return FI_OK;
+}
+int fi_jpeg_decode_device(fi_ctx *c, const uint8_t *const *data, const size_t *len, int32_t n, uint8_t *const *dst,
+                          const int64_t *dst_stride, int32_t out_channels, int32_t *status) {
+  return fi_jpeg_decode_device_ex(c, data, len, n, dst, dst_stride, out_channels, 0, status);
+}
+// Test hook: a progressive stream's coefficients from the host decoder
+// (fi_jpeg_prog_host.cpp): info = {components, bw[3], bh[3]}; qt = the quant
+// table of each component, natural order; coefs (may be NULL: sizes only) =
+// the zigzag int16 blocks of component 0, 1, 2, [bh][bw][64] each
+int fi_debug_jpeg_coefs_host(const uint8_t *data, size_t len, uint32_t flags, int32_t info[7], uint16_t qt[192],
+                             int16_t *coefs, size_t coefs_cap) {
+  if (!data || !info || !qt) return set_err(FI_EINVAL, "bad arguments");
+  JpegHdr H;
+  JpegGeom G;
+  std::vector<int16_t> co;
+  const int rc = jpeg_prog_coefs_host(data, len, flags, &H, &G, &co);
+  if (rc) return set_err(rc, rc == FI_EUNSUPPORTED ? "not a progressive stream the decoder handles" : "malformed JPEG");
+  info[0] = H.ncomp;
+  for (int k = 0; k < 3; k++) {
+    info[1 + k] = G.bw[k];
+    info[4 + k] = G.bh[k];
+    for (int z = 0; z < 64; z++) qt[64 * k + z] = k < H.ncomp ? H.qt[H.tq[k]][z] : 0;
+  }
+  if (coefs) {
+    if (coefs_cap < co.size()) return set_err(FI_ENOMEM, "coefs_cap is below the coefficient count");
+    memcpy(coefs, co.data(), co.size() * sizeof(int16_t));
+  }
+  return FI_OK;
+}
+// GPU JPEG encode (fi_jpeg_enc.hip): the write half of `convert` (IM writes the
+// output with libjpeg) on the device
+int fi_jpeg_encode_bound(int32_t w, int32_t h, int32_t channels, int32_t quality, int32_t subsampling, size_t *bytes) {
+  if (!bytes) return set_err(FI_EINVAL, "bad arguments");
+  const int rc = jpeg_enc_bound(w, h, channels, quality, subsampling, bytes);
+  if (rc)
+    return set_err(rc, rc == FI_EUNSUPPORTED ? "channel count or subsampling the GPU JPEG encoder does not write"
+                                             : "bad JPEG dimensions or quality");
+  return FI_OK;
+}
+static void *jpeg_enc_alloc(void *actx, int which, size_t bytes) {
+  fi_ctx *c = static_cast<fi_ctx *>(actx);
+  if (which == 3)  // pinned host staging (no copy of an earlier request is in flight: see jpeg_encode_batch)
+    return ensure_pinned_buf(&c->jpeg_enc_host, &c->jpeg_enc_host_cap, bytes) == FI_OK ? c->jpeg_enc_host : nullptr;
+  return ensure(c, &c->jpeg_enc[which], bytes) == FI_OK ? c->jpeg_enc[which].p : nullptr;
+}
+static void jpeg_enc_stage(void *actx, const char *name) {  // ends the running kernel's range, starts `name`'s
+  fi_ctx *c = static_cast<fi_ctx *>(actx);
+  delete c->jpeg_enc_timer;
+  c->jpeg_enc_timer = name ? new Timer(c, name, 0) : nullptr;
+}
+int fi_jpeg_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                          const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
+                          const int32_t *subsampling, int32_t n, uint8_t *const *out, const size_t *out_cap,
+                          size_t *out_len, int32_t *status) {
+  if (!c || n < 0 ||
+      (n > 0 && (!src || !w || !h || !channels || !src_stride || !quality || !subsampling || !out || !out_cap ||
+                 !out_len || !status)))
+    return set_err(FI_EINVAL, "bad arguments");
+  if (n == 0) return FI_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
+  std::string err;
+  const int rc = jpeg_encode_batch(c->stream, src, w, h, channels, src_stride, quality, subsampling, n, out, out_cap,
+                                   out_len, status, jpeg_enc_alloc, jpeg_enc_stage, c, &err);
+  jpeg_enc_stage(c, nullptr);
+  collect_timers(c);
+  if (rc) return set_err(rc, "%s", err.c_str());
+  for (int i = 0; i < n; i++)  // the others are encoded
+    if (status[i])
+      return set_err(status[i], "image %d: %s", i,
+                     status[i] == FI_EUNSUPPORTED ? "channel count or subsampling the GPU JPEG encoder does not write"
+                     : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
+                                                  : "bad JPEG source, dimensions or quality");
+  return FI_OK;
+}
+
+}  // extern "C"

@@ -384,7 +384,11 @@ int fi_debug_skinsat(fi_ctx *ctx, const fi_smartcrop_params *params, uint16_t *o
  * a serving context's): (NULL, 0, ...) drops it, (NULL, 1, ...) clears its
  * statistics, (NULL, 2, 0, ms) reads the resample plan's counters since:
  * ms[0] images planned onto k_rs_vr, ms[1] vertical-first images, ms[2]
- * k_rs_vr launches. */
+ * k_rs_vr launches; (NULL, 3, 0, ms) reads what the last planned batch
+ * emitted: ms[0], ms[1] the low and high 32 bits of a 64-bit FNV-1a digest of
+ * the packed upload blob followed by the workspace size (eight bytes, low
+ * first), ms[2] the blob's bytes, ms[3..5] the k_rs_vm, k_rs_vr and k_rs_hv
+ * tiles, ms[6] the smartcrop items. */
 int fi_debug_host_plan(const fi_image *imgs, int32_t n, int32_t iters, double *ms);
 
 #ifdef __cplusplus

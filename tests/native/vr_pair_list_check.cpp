@@ -1,5 +1,5 @@
 // The pair-class copies of k_rs_vr's uneven touched-row list (fi_internal.h
-// vr_pair_off, laid out by fi_api.cpp build_vr_tiles, read by the loader waves
+// vr_pair_off, laid out by fi_tiles.cpp build_vr_tiles, read by the loader waves
 // in fi_vr.hip): for 2 and 4 loader waves (C = 2 NL rows between a wave's own
 // pairs) every pair start k has its own two slots, inside the copy, the C = 8
 // copy after the C = 4 one, and a wave's own pairs k, k + C, k + 2C, ... at

@@ -1,7 +1,7 @@
 """Stream ordering of the batch pipeline on the GPU (MI355X), through the C-ABI.
 
 The crop apply of batch k runs on its own stream beside batch k+1's resample
-(fi_api.cpp launch_batch); the RCCL record gather runs on a stream of its own
+(fi_batch.cpp launch_batch); the RCCL record gather runs on a stream of its own
 (fi_rccl_gather_start / _finish).  These tests pin what the header promises
 across those streams:
 

@@ -9,14 +9,14 @@ from flyimg_amd.processor import ImageProcessor, OptionsBag
 from flyimg_amd.runtime import plan as fi_plan
 
 
-def _batch(items):
+def _batch(items, stride_align=16):
     arr = (L.FiImage * len(items))()
     addr = 1 << 36
     for i, (W, H, opts) in enumerate(items):
         op = ImageProcessor(OptionsBag(opts), W, H).to_op()
         ow, oh, oc = fi_plan(W, H, op)
         a = arr[i]
-        stride = (W * 3 + 15) // 16 * 16
+        stride = (W * 3 + stride_align - 1) // stride_align * stride_align
         a.src, a.src_w, a.src_h, a.src_stride, a.src_channels = addr, W, H, stride, 3
         addr += (stride * H + 255) // 256 * 256
         a.target_w, a.target_h, a.flags, a.gravity, a.rotate = op.target_w, op.target_h, op.flags, op.gravity, op.rotate

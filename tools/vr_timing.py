@@ -45,7 +45,7 @@ with Context(0) as ctx:
     a = buf.reshape(256, 16, 6).astype(np.float64)
     a = a[a[:, 0, 5] > 0]
     ph = a[:, 0, 5].mean()
-    nl = int(os.environ.get("VR_NL", "2"))  # the launch's loader waves (fi_api.cpp picks 4 for one-block strips)
+    nl = int(os.environ.get("VR_NL", "2"))  # the launch's loader waves (fi_tiles.cpp picks 4 for one-block strips)
     roles = {"V": (range(0, 8), ["tile entry", "V-MFMA issue", "planes", "barrier", "plane wait"]),
              "H": (range(8, 15 - nl), ["-", "tile entry", "horizontal", "-", "barrier"]),
              "L": (range(16 - nl, 16), ["A DMA", "records + row DMA", "vmcnt wait", "barrier"])}
