@@ -93,6 +93,11 @@ class FiCropScore(ctypes.Structure):
     ]
 
 
+class FiJpegView(ctypes.Structure):
+    """fi_jpeg_view: EXIF orientation (0 = the file's) + rectangle of the oriented image (all 0 = whole)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("orientation", "x", "y", "w", "h")]
+
+
 class FiRecord(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in
                 ("image", "status", "out_w", "out_h", "crop_x", "crop_y", "crop_w", "crop_h")]
@@ -197,6 +202,8 @@ def lib():
     L.fi_jpeg_info_ex.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, P(i32), P(i32), P(i32), P(i32),
                                   P(i32)]
     L.fi_jpeg_decode_device_ex.argtypes = [vp, vp, vp, i32, vp, vp, i32, ctypes.c_uint32, vp]
+    L.fi_jpeg_orientation.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(i32)]
+    L.fi_jpeg_decode_device_view.argtypes = [vp, vp, vp, i32, vp, vp, i32, ctypes.c_uint32, P(FiJpegView), vp]
     L.fi_debug_jpeg_coefs_host.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, vp, vp, vp,
                                            ctypes.c_size_t]
     L.fi_jpeg_encode_bound.argtypes = [i32, i32, i32, i32, i32, P(ctypes.c_size_t)]

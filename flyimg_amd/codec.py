@@ -110,21 +110,28 @@ class _PinnedSlot:
         return self._slices(buf, sizes)
 
 
-def gpu_decodable(blob: bytes, progressive: bool = False):
+def gpu_decodable(blob: bytes, progressive: bool = False, orient: bool = False):
     """(width, height, source channels) when the GPU decoder
     (fi_jpeg_decode_device, RGB output) produces exactly what decode_ex would:
     a baseline gray or YCbCr JPEG (fi_jpeg_info) with no EXIF rotation to
     apply; None otherwise (progressive, CMYK, PNG, ...).  A gray (1-component)
     JPEG is an IM PseudoClass source, as decode_ex flags it.  With
     ``progressive`` complete Huffman progressive JPEGs qualify as well
-    (fi_jpeg_info_ex / fi_jpeg_decode_device_ex, FI_JPEG_PROGRESSIVE)."""
-    from PIL import Image
-
-    from .runtime import jpeg_info
+    (fi_jpeg_info_ex / fi_jpeg_decode_device_ex, FI_JPEG_PROGRESSIVE).  With
+    ``orient`` EXIF-rotated files qualify too, for a decode through a view
+    (fi_jpeg_decode_device_view, orientation 0): the ORIENTED (width, height,
+    channels) of every file whose orientation the library determines
+    (fi_jpeg_orientation), None for the others."""
+    from .runtime import jpeg_info, jpeg_orientation, jpeg_view_dims
 
     info = jpeg_info(blob, progressive)
     if not info:
         return None
+    if orient:
+        o = jpeg_orientation(blob)
+        return jpeg_view_dims(info[0], info[1], (o, 0, 0, 0, 0)) + (info[2],) if o else None
+    from PIL import Image
+
     try:
         orientation = Image.open(io.BytesIO(blob)).getexif().get(0x0112, 1)  # headers only
     except Exception:  # noqa: BLE001 - unreadable EXIF: let the host path decide
@@ -146,15 +153,23 @@ class CodecPipeline:
     scan is one serial chain on the GPU: measured on 1080p sources the GPU
     path loses to 16 host threads below about 220 images per batch (172
     against 403 img/s at batches of 64) and wins above (1956 against 652
-    img/s at 1024 images); DESIGN.md 3.5."""
+    img/s at 1024 images); DESIGN.md 3.5.  With ``gpu_orient`` (off by
+    default) EXIF-rotated JPEGs and ``e_1`` extracts join the GPU decode batch
+    as well: the decoder's colour stage applies ``-auto-orient`` and
+    ExtractProcessor's rectangle (fi_jpeg_decode_device_view), so each device
+    buffer holds the oriented, extracted source (same pixels as the host
+    path's).  ``decode_stats`` counts the images ``process`` decoded on each
+    side."""
 
     def __init__(self, ctx, threads: int = 16, gpu_decode: bool = True, gpu_encode: bool = False,
-                 gpu_progressive: bool = False):
+                 gpu_progressive: bool = False, gpu_orient: bool = False):
         self.ctx = ctx
         self.pool = ThreadPoolExecutor(max_workers=max(1, threads))
         self.gpu_decode = gpu_decode
         self.gpu_encode = gpu_encode
         self.gpu_progressive = gpu_progressive
+        self.gpu_orient = gpu_orient
+        self.decode_stats = {"gpu": 0, "host": 0}  # images ``process`` decoded on the GPU / on the host
         # ``process``: host seconds in the encode stage, the bytes its outputs
         # were as pixels and are as files (with gpu_encode, what crosses PCIe)
         self.process_stats = {"s_encode": 0.0, "raw_bytes": 0, "encoded_bytes": 0}
@@ -181,9 +196,10 @@ class CodecPipeline:
         outs, recs, _ = self.ctx.process(srcs, ops)
         return outs, list(recs)
 
-    def _gpu_batch(self, blobs, bags, dims, held=None):
+    def _gpu_batch(self, blobs, bags, dims, held=None, views=None):
         """GPU decode into one device pool (16-B aligned rows for the streaming
-        resample kernels), one device batch.
+        resample kernels), one device batch.  ``views`` (gpu_orient): the
+        decode view of each image, ``dims`` then being what it decodes to.
         Returns (outputs, records, indices the GPU decoder turned down).  With
         ``held`` (a list) the outputs stay on the device: they come back as
         (device pointer, w, h, stride, channels) views and their allocation is
@@ -193,7 +209,8 @@ class CodecPipeline:
         base = self.ctx.malloc(int(offs[-1]))
         try:
             ptrs = [base + int(o) for o in offs[:-1]]
-            status = self.ctx.jpeg_decode(blobs, ptrs, strides, channels=3, progressive=self.gpu_progressive)
+            status = self.ctx.jpeg_decode(blobs, ptrs, strides, channels=3, progressive=self.gpu_progressive,
+                                          views=views)
             views, ops, keep = [], [], []
             for i, (bag, (w, h, c), p, st) in enumerate(zip(bags, dims, ptrs, strides)):
                 if status[i] != L.FI_OK:
@@ -264,16 +281,37 @@ class CodecPipeline:
         # extract (e_1) views start at any byte: the host path copies them to an
         # aligned array, so they decode there and take the same kernels
         # (bag.get: extract_key would consume the option, as InputImage::extractKey does)
-        dims = [gpu_decodable(b, self.gpu_progressive) if self.gpu_decode and _empty(bag.get("extract")) else None
-                for b, bag in zip(blobs, bags)]
+        views = None
+        if self.gpu_decode and self.gpu_orient:
+            # ... unless the decoder applies the view itself: orientation from the
+            # file, ExtractProcessor's rectangle of the oriented image
+            dims, views = [None] * n, [None] * n
+            for i, (b, bag) in enumerate(zip(blobs, bags)):
+                d = gpu_decodable(b, self.gpu_progressive, orient=True)
+                if d is None:
+                    continue
+                rect = (0, 0, 0, 0)
+                if not _empty(bag.extract_key("extract")):  # (as ExtractProcessor.extract)
+                    rect = ExtractProcessor.rectangle(bag, d[0], d[1])
+                    d = (rect[2], rect[3], d[2])
+                dims[i], views[i] = d, (0,) + rect
+        else:
+            dims = [gpu_decodable(b, self.gpu_progressive) if self.gpu_decode and _empty(bag.get("extract")) else None
+                    for b, bag in zip(blobs, bags)]
         host = [i for i in range(n) if dims[i] is None]
         gpu = [i for i in range(n) if dims[i] is not None]
         if gpu:
             o, r, back = self._gpu_batch([blobs[i] for i in gpu], [bags[i] for i in gpu], [dims[i] for i in gpu],
-                                         held if self.gpu_encode else None)
+                                         held if self.gpu_encode else None,
+                                         [views[i] for i in gpu] if views else None)
             for k, i in enumerate(gpu):
                 outs[i], recs[i] = o[k], r[k]
             host += [gpu[k] for k in back]
+            if views:  # (the view consumed their extract keys: the host path extracts from a fresh bag)
+                for k in back:
+                    bags[gpu[k]] = OptionsBag(options[gpu[k]])
+        self.decode_stats["gpu"] += n - len(host)
+        self.decode_stats["host"] += len(host)
         if host:
             o, r = self._host_batch([blobs[i] for i in host], [bags[i] for i in host])
             for k, i in enumerate(host):

@@ -422,6 +422,16 @@ struct JpegDesc {        // one image of a decode batch
 struct JpegInterval {    // one restart interval: its MCUs and where its bits start
   int32_t img, mcu0, mcu1, byte0;
 };
+// An image decoded through a view (k_jpeg_color_view, fi_jpeg_view.h): EXIF
+// orientation o applied, then the rectangle (x, y, w, h) of the oriented image
+// written to the descriptor's dst as h rows of w pixels.
+constexpr int kJpegViewTile = 32;  // work item: one kJpegViewTile^2 tile of the rectangle
+struct JpegViewDesc {
+  int32_t img;           // descriptor index
+  int32_t o, x, y, w, h;
+  int32_t tiles_x;       // tiles per row of the rectangle
+  int32_t pad;
+};
 // Progressive streams (k_jpeg_prog): one work item per (image, scan, restart
 // interval).  A single-component scan walks the component's own block raster
 // (`mcux` blocks per row, one block per MCU); an interleaved DC scan walks the

@@ -55,6 +55,13 @@ bool jpeg_build_huff(const std::string &dht, bool dc, JpegHuff *t);
 // dimensions and output channels of a stream the GPU decoder takes
 int jpeg_info(const uint8_t *data, size_t len, int *w, int *h, int *c);
 int jpeg_info_ex(const uint8_t *data, size_t len, uint32_t flags, int *w, int *h, int *c, int *nscans, int *nlevels);
+// EXIF orientation of a JPEG as Pillow's Image.getexif().get(0x0112, 1) reads
+// it, from the marker segments up to the first SOS (whether or not the GPU
+// decoder takes the stream): FI_OK with *orientation in 1..8 (values
+// exif_transpose ignores are 1); FI_EUNSUPPORTED where Pillow's answer takes
+// more than an IFD0 lookup (several Exif segments, XMP, odd types, malformed
+// TIFF): the host decides; FI_EINVAL without SOI
+int jpeg_orientation(const uint8_t *d, size_t n, int *orientation);
 void jpeg_geom(const JpegHdr &H, JpegGeom *G);
 // The work items of a progressive stream: per scan, one per restart interval
 // (located by the RSTn markers of the scan's segment).  tabmap[i] = the batch

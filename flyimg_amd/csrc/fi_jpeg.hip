@@ -15,7 +15,11 @@
 //            (dequantise, 13-bit constants, PASS1_BITS 2, range limit);
 //   k_jpeg_color  one thread per output pixel: jdsample.c fancy upsampling
 //            (h2v1 / h2v2 triangle filters, edge replication) and jdcolor.c
-//            ycc_rgb_convert with its 16-bit fixed-point tables.
+//            ycc_rgb_convert with its 16-bit fixed-point tables;
+//   k_jpeg_color_view  the same stage for the images decoded through a view
+//            (fi_jpeg_decode_device_view: an EXIF orientation and a rectangle
+//            of the oriented image), one workgroup per 32x32 output tile, the
+//            transposing orientations through LDS.
 //
 // Unsupported streams (progressive, arithmetic, 12-bit, CMYK / Adobe
 // transforms, other samplings, several scans) return FI_EUNSUPPORTED from
@@ -46,6 +50,7 @@
 #include "fi_internal.h"
 #include "fi_jpeg.h"
 #include "fi_jpeg_prog.h"
+#include "fi_jpeg_view.h"
 
 namespace fi {
 
@@ -559,6 +564,21 @@ __device__ __forceinline__ int jpeg_up(const uint8_t *pl, int pitch, int dw, int
 }
 __device__ __forceinline__ uint8_t jpeg_clamp(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
 
+// Pixel (x, y) of a YCbCr image from its luma sample Y: fancy-upsampled chroma
+// and jdcolor.c ycc_rgb_convert, as R | G << 8 | B << 16 (both colour kernels)
+__device__ __forceinline__ uint32_t jpeg_ycc_rgb(const JpegDesc &D, const uint8_t *__restrict__ work, int Y, int x,
+                                                 int y) {
+  const int hs = D.h[0], vs = D.v[0];
+  const int cb = jpeg_up(work + D.plane[1], D.bw[1] * 8, D.dw[1], D.dh[1], hs, vs, x, y);
+  const int cr = jpeg_up(work + D.plane[2], D.bw[2] * 8, D.dw[2], D.dh[2], hs, vs, x, y);
+  // build_ycc_rgb_table: FIX(x) = (int)(x * 65536 + 0.5), ONE_HALF = 1 << 15
+  const int xr = cr - 128, xb = cb - 128;
+  const int r = Y + ((91881 * xr + 32768) >> 16);
+  const int g = Y + ((-22554 * xb + 32768 + -46802 * xr) >> 16);
+  const int b = Y + ((116130 * xb + 32768) >> 16);
+  return (uint32_t)jpeg_clamp(r) | (uint32_t)jpeg_clamp(g) << 8 | (uint32_t)jpeg_clamp(b) << 16;
+}
+
 __device__ __forceinline__ void jpeg_color_px(const JpegDesc *__restrict__ descs, const int64_t *__restrict__ px0,
                                               int nimg, const uint8_t *__restrict__ work, int64_t i) {
   // image of pixel i: binary search over the per-image pixel prefix
@@ -581,18 +601,11 @@ __device__ __forceinline__ void jpeg_color_px(const JpegDesc *__restrict__ descs
     for (int k = 0; k < D.dst_c; k++) o[k] = Y;
     return;
   }
-  const int hs = D.h[0], vs = D.v[0];
-  const int cb = jpeg_up(work + D.plane[1], D.bw[1] * 8, D.dw[1], D.dh[1], hs, vs, x, y);
-  const int cr = jpeg_up(work + D.plane[2], D.bw[2] * 8, D.dw[2], D.dh[2], hs, vs, x, y);
-  // build_ycc_rgb_table: FIX(x) = (int)(x * 65536 + 0.5), ONE_HALF = 1 << 15
-  const int xr = cr - 128, xb = cb - 128;
-  const int r = Y + ((91881 * xr + 32768) >> 16);
-  const int g = Y + ((-22554 * xb + 32768 + -46802 * xr) >> 16);
-  const int b = Y + ((116130 * xb + 32768) >> 16);
+  const uint32_t p = jpeg_ycc_rgb(D, work, Y, x, y);
   uint8_t *o = D.dst + (int64_t)y * D.dst_stride + 3 * x;
-  o[0] = jpeg_clamp(r);
-  o[1] = jpeg_clamp(g);
-  o[2] = jpeg_clamp(b);
+  o[0] = (uint8_t)p;
+  o[1] = (uint8_t)(p >> 8);
+  o[2] = (uint8_t)(p >> 16);
 }
 
 // (grid-stride: a dispatch's work-item count is 32-bit, a batch may hold more pixels)
@@ -602,6 +615,81 @@ __global__ __launch_bounds__(256) void k_jpeg_color(const JpegDesc *__restrict__
     jpeg_color_px(descs, px0, nimg, work, i);
 }
 
+// The colour stage of the images decoded through a view (fi_jpeg_view.h): the
+// same pixels, written where the oriented, extracted image wants them.  One
+// 256-thread workgroup per (image, 32x32 tile of the output rectangle); vt0 =
+// the per-view tile prefix (binary search, the grid strides over the items as
+// k_jpeg_color does over px0).
+//   o 1..4  lanes run along the output row: plane reads and dst writes are both
+//           row-contiguous (reversed for a flip), no LDS;
+//   o 5..8  phase 1: lanes run along the SOURCE row (consecutive lanes read
+//           consecutive luma bytes) and write the pixel, one dword, to an LDS
+//           tile [source row][source column] of 33-dword rows; one barrier;
+//           phase 2: lanes run along the OUTPUT row, reading the tile
+//           column-wise (odd pitch: 32 lanes on 32 banks) -- no lane walks a
+//           plane column and no wave scatters over 64 rows of dst.
+// Chroma neighbours outside the rectangle come from the full planes (edge
+// replication at the image edges only); only bytes [0, w * dst_c) of the h
+// rows are written.
+__device__ __forceinline__ uint32_t jpeg_view_px(const JpegDesc &D, const uint8_t *__restrict__ work, int sx, int sy) {
+  const int Y = work[D.plane[0] + (int64_t)sy * (D.bw[0] * 8) + sx];
+  if (D.ncomp == 1) return (uint32_t)Y * 0x010101u;
+  return jpeg_ycc_rgb(D, work, Y, sx, sy);
+}
+__device__ __forceinline__ void jpeg_view_store(const JpegDesc &D, const JpegViewDesc &V, int u, int v, uint32_t p) {
+  uint8_t *o = D.dst + (int64_t)(v - V.y) * D.dst_stride + (int64_t)(u - V.x) * D.dst_c;
+  o[0] = (uint8_t)p;
+  if (D.dst_c == 3) {
+    o[1] = (uint8_t)(p >> 8);
+    o[2] = (uint8_t)(p >> 16);
+  }
+}
+__global__ __launch_bounds__(256) void k_jpeg_color_view(const JpegDesc *__restrict__ descs,
+                                                         const JpegViewDesc *__restrict__ views,
+                                                         const int64_t *__restrict__ vt0, int nview,
+                                                         const uint8_t *__restrict__ work) {
+  constexpr int T = kJpegViewTile, P = T + 1;
+  __shared__ uint32_t tile[T * P];
+  const int cx = threadIdx.x & (T - 1), cy = threadIdx.x / T;  // 8 rows of 32 lanes per pass
+  for (int64_t item = blockIdx.x; item < vt0[nview]; item += gridDim.x) {
+    int lo = 0, hi = nview;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (vt0[mid] <= item)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    const JpegViewDesc V = views[lo];
+    const JpegDesc &D = descs[V.img];
+    const int t = (int)(item - vt0[lo]);
+    const int ty = t / V.tiles_x, tx = t - ty * V.tiles_x;
+    const int u0 = V.x + tx * T, v0 = V.y + ty * T;  // the tile in the oriented image
+    const int tw = min(T, V.x + V.w - u0), th = min(T, V.y + V.h - v0);
+    if (!jpeg_view_transposed(V.o)) {
+      if (cx < tw)
+        for (int r = cy; r < th; r += 256 / T) {
+          int sx, sy;
+          jpeg_view_map(V.o, D.W, D.H, u0 + cx, v0 + r, &sx, &sy);
+          jpeg_view_store(D, V, u0 + cx, v0 + r, jpeg_view_px(D, work, sx, sy));
+        }
+      continue;
+    }
+    // phase 1: lane cx along the source row = the output column's direction v, row r of the pass = u
+    if (cx < th)
+      for (int r = cy; r < tw; r += 256 / T) {
+        int sx, sy;
+        jpeg_view_map(V.o, D.W, D.H, u0 + r, v0 + cx, &sx, &sy);
+        tile[r * P + cx] = jpeg_view_px(D, work, sx, sy);
+      }
+    __syncthreads();
+    // phase 2: lane cx along the output row
+    if (cx < tw)
+      for (int r = cy; r < th; r += 256 / T) jpeg_view_store(D, V, u0 + cx, v0 + r, tile[cx * P + r]);
+    if (item + gridDim.x < vt0[nview]) __syncthreads();  // (the block's next tile overwrites the LDS tile)
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host: batch plan + launches
 // ---------------------------------------------------------------------------
@@ -609,9 +697,9 @@ __global__ __launch_bounds__(256) void k_jpeg_color(const JpegDesc *__restrict__
 // stays valid until the stream has run: 0 device upload (compressed data +
 // tables), 2 device work (coefficients + planes), 3 pinned host staging.
 int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *len, int n, uint8_t *const *dst,
-                      const int64_t *dst_stride, int out_channels, uint32_t flags, int32_t *status,
-                      void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *), void *actx,
-                      std::string *err) {
+                      const int64_t *dst_stride, int out_channels, uint32_t flags, const fi_jpeg_view *views,
+                      int32_t *status, void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *),
+                      void *actx, std::string *err) {
   std::vector<JpegHdr> hd(n);
   std::vector<int> ok(n, 0);
   std::map<std::string, int> huff_ix;
@@ -625,7 +713,9 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   size_t pcoef_total = 0;            // their coefficient planes: one region at the end of the work buffer, zeroed
   std::vector<int64_t> blk0;  // first block of each (image, component)
   int64_t nblocks = 0;
-  std::vector<int64_t> px0(1, 0);
+  std::vector<int64_t> px0(1, 0);     // k_jpeg_color's pixels: the images without a view
+  std::vector<JpegViewDesc> vds;      // k_jpeg_color_view's: the others, and their tile prefix
+  std::vector<int64_t> vt0(1, 0);
   size_t ecs_total = 0, work_total = 0;
   // header parse (incl. the scan for the end of each entropy-coded segment)
   // and, below, the staging copies run on a few host threads
@@ -643,10 +733,37 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
       });
     for (auto &t : th) t.join();
   };
-  parallel(n, [&](int i) { status[i] = jpeg_parse(data[i], len[i], &hd[i], flags); });
+  // a view's orientation: given, or (0) the file's; undetermined: that image decodes on the host
+  std::vector<int> orient(n, 1);
+  parallel(n, [&](int i) {
+    status[i] = jpeg_parse(data[i], len[i], &hd[i], flags);
+    if (!views) return;
+    orient[i] = views[i].orientation;
+    if (orient[i] < 0 || orient[i] > 8)
+      status[i] = FI_EINVAL;
+    else if (orient[i] == 0 && !status[i] && jpeg_orientation(data[i], len[i], &orient[i]) != FI_OK)
+      status[i] = FI_EUNSUPPORTED;
+  });
   for (int i = 0; i < n; i++) {
     if (status[i]) continue;
     JpegHdr &H = hd[i];
+    // the view's rectangle, inside the oriented image (all 0: the whole of it)
+    JpegViewDesc V{};
+    V.o = orient[i];
+    if (views) {
+      const fi_jpeg_view &R = views[i];
+      const int ow = jpeg_view_transposed(V.o) ? H.H : H.W, oh = jpeg_view_transposed(V.o) ? H.W : H.H;
+      const bool whole = R.x == 0 && R.y == 0 && R.w == 0 && R.h == 0;
+      if (!whole && (R.x < 0 || R.y < 0 || R.w <= 0 || R.h <= 0 || R.x > ow - R.w || R.y > oh - R.h)) {
+        status[i] = FI_EINVAL;
+        continue;
+      }
+      V.x = R.x;
+      V.y = R.y;
+      V.w = whole ? ow : R.w;
+      V.h = whole ? oh : R.h;
+      if (whole && V.o == 1) V.w = V.h = 0;  // no view: k_jpeg_color, as without `views`
+    }
     JpegDesc D{};
     D.W = H.W;
     D.H = H.H;
@@ -746,7 +863,15 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
       blk0.push_back(nblocks);
       if (c < H.ncomp) nblocks += (int64_t)D.bw[c] * D.bh[c];
     }
-    px0.push_back(px0.back() + (int64_t)H.W * H.H);
+    if (V.w > 0) {
+      V.img = img;
+      V.tiles_x = (V.w + kJpegViewTile - 1) / kJpegViewTile;
+      vds.push_back(V);
+      vt0.push_back(vt0.back() + (int64_t)V.tiles_x * ((V.h + kJpegViewTile - 1) / kJpegViewTile));
+      px0.push_back(px0.back());
+    } else {
+      px0.push_back(px0.back() + (int64_t)H.W * H.H);
+    }
     // zero pad: the reader's window (a progressive scan's reader stops at its scan's end, inside the segment)
     ecs_total += ((size_t)D.ecs_len + 512 + 255) & ~(size_t)255;
     descs.push_back(D);
@@ -773,7 +898,9 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   const size_t o_qt = o_huff + ((huffs.size() * sizeof(JpegHuff) + 255) & ~(size_t)255);
   const size_t o_px = o_qt + ((qts.size() * 2 + 255) & ~(size_t)255);
   const size_t o_pit = o_px + ((px0.size() * 8 + 255) & ~(size_t)255);
-  const size_t tab0 = (ecs_total + 255) & ~(size_t)255, up_total = tab0 + o_pit + pitems.size() * sizeof(JpegProgItem);
+  const size_t o_view = o_pit + ((pitems.size() * sizeof(JpegProgItem) + 255) & ~(size_t)255);
+  const size_t o_vt = o_view + ((vds.size() * sizeof(JpegViewDesc) + 255) & ~(size_t)255);
+  const size_t tab0 = (ecs_total + 255) & ~(size_t)255, up_total = tab0 + o_vt + vt0.size() * 8;
   uint8_t *din = (uint8_t *)alloc(actx, 0, up_total);
   uint8_t *hst = (uint8_t *)alloc(actx, 3, up_total);
   uint8_t *dwork = (uint8_t *)alloc(actx, 2, std::max(work_total, (size_t)256));
@@ -798,6 +925,8 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   memcpy(htab + o_qt, qts.data(), qts.size() * 2);
   memcpy(htab + o_px, px0.data(), px0.size() * 8);
   if (!pitems.empty()) memcpy(htab + o_pit, pitems.data(), pitems.size() * sizeof(JpegProgItem));
+  if (!vds.empty()) memcpy(htab + o_view, vds.data(), vds.size() * sizeof(JpegViewDesc));
+  memcpy(htab + o_vt, vt0.data(), vt0.size() * 8);
   if (hipMemcpyAsync(din, hst, up_total, hipMemcpyHostToDevice, st) != hipSuccess) {
     *err = "JPEG batch upload";
     return FI_EDEVICE;
@@ -832,8 +961,18 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   }
   hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)std::min<int64_t>((nblocks + 255) / 256, 1 << 20)), dim3(256), 0, st, dd,
                      (const int64_t *)(dtab + o_ref), (int)descs.size(), (const uint16_t *)(dtab + o_qt), dwork);
-  hipLaunchKernelGGL(k_jpeg_color, dim3((unsigned)std::min<int64_t>((px0.back() + 255) / 256, 1 << 20)), dim3(256), 0, st, dd,
-                     (const int64_t *)(dtab + o_px), (int)descs.size(), dwork);
+  if (px0.back() > 0) {
+    if (stage) stage(actx, "k_jpeg_color");
+    hipLaunchKernelGGL(k_jpeg_color, dim3((unsigned)std::min<int64_t>((px0.back() + 255) / 256, 1 << 20)), dim3(256), 0, st, dd,
+                       (const int64_t *)(dtab + o_px), (int)descs.size(), dwork);
+    if (stage) stage(actx, nullptr);
+  }
+  if (!vds.empty()) {  // the images with a view: their own colour kernel, one workgroup per output tile
+    if (stage) stage(actx, "k_jpeg_color_view");
+    hipLaunchKernelGGL(k_jpeg_color_view, dim3((unsigned)std::min<int64_t>(vt0.back(), 1 << 20)), dim3(256), 0, st, dd,
+                       (const JpegViewDesc *)(dtab + o_view), (const int64_t *)(dtab + o_vt), (int)vds.size(), dwork);
+    if (stage) stage(actx, nullptr);
+  }
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
     *err = "JPEG decode kernels";
     return FI_EDEVICE;

@@ -33,8 +33,18 @@ static void *jpeg_alloc(void *actx, int which, size_t bytes) {
   return ensure(c, &c->jpeg[which], bytes) == FI_OK ? c->jpeg[which].p : nullptr;
 }
 static void jpeg_enc_stage(void *actx, const char *name);
-int fi_jpeg_decode_device_ex(fi_ctx *c, const uint8_t *const *data, const size_t *len, int32_t n, uint8_t *const *dst,
-                             const int64_t *dst_stride, int32_t out_channels, uint32_t flags, int32_t *status) {
+int fi_jpeg_orientation(const uint8_t *data, size_t len, int32_t *orientation) {
+  if (!data || !orientation) return set_err(FI_EINVAL, "bad arguments");
+  int o = 1;
+  const int rc = jpeg_orientation(data, len, &o);
+  if (rc)
+    return set_err(rc, rc == FI_EUNSUPPORTED ? "EXIF orientation to be read on the host" : "not a JPEG");
+  *orientation = o;
+  return FI_OK;
+}
+int fi_jpeg_decode_device_view(fi_ctx *c, const uint8_t *const *data, const size_t *len, int32_t n, uint8_t *const *dst,
+                               const int64_t *dst_stride, int32_t out_channels, uint32_t flags,
+                               const fi_jpeg_view *views, int32_t *status) {
   if (!c || n < 0 || (n > 0 && (!data || !len || !dst || !dst_stride || !status)) ||
       (out_channels != 0 && out_channels != 3) || (flags & ~FI_JPEG_PROGRESSIVE))
     return set_err(FI_EINVAL, "bad arguments");
@@ -43,17 +53,22 @@ int fi_jpeg_decode_device_ex(fi_ctx *c, const uint8_t *const *data, const size_t
   std::lock_guard<std::mutex> lk(c->mu);
   if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
   std::string err;
-  // (the stage callback times k_jpeg_prog the way the encode kernels are timed)
-  const int rc = jpeg_decode_batch(c->stream, data, len, n, dst, dst_stride, out_channels, flags, status, jpeg_alloc,
-                                   jpeg_enc_stage, c, &err);
+  // (the stage callback times k_jpeg_prog and the colour kernels the way the encode kernels are timed)
+  const int rc = jpeg_decode_batch(c->stream, data, len, n, dst, dst_stride, out_channels, flags, views, status,
+                                   jpeg_alloc, jpeg_enc_stage, c, &err);
   jpeg_enc_stage(c, nullptr);
   collect_timers(c);
   if (rc) return set_err(rc, "%s", err.c_str());
   for (int i = 0; i < n; i++)  // the others are decoded; the caller decodes these on the host
     if (status[i])
       return set_err(status[i], "image %d: %s", i,
-                     status[i] == FI_EUNSUPPORTED ? "JPEG stream the GPU decoder does not handle" : "malformed JPEG");
+                     status[i] == FI_EUNSUPPORTED ? "JPEG stream or EXIF orientation the GPU decoder does not handle"
+                                                  : "malformed JPEG or bad view");
   return FI_OK;
+}
+int fi_jpeg_decode_device_ex(fi_ctx *c, const uint8_t *const *data, const size_t *len, int32_t n, uint8_t *const *dst,
+                             const int64_t *dst_stride, int32_t out_channels, uint32_t flags, int32_t *status) {
+  return fi_jpeg_decode_device_view(c, data, len, n, dst, dst_stride, out_channels, flags, nullptr, status);
 }
 int fi_jpeg_decode_device(fi_ctx *c, const uint8_t *const *data, const size_t *len, int32_t n, uint8_t *const *dst,
                           const int64_t *dst_stride, int32_t out_channels, int32_t *status) {

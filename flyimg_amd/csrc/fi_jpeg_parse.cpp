@@ -412,6 +412,76 @@ int jpeg_info(const uint8_t *data, size_t len, int *w, int *h, int *c) {
   return jpeg_info_ex(data, len, 0, w, h, c, nullptr, nullptr);
 }
 
+// ---- EXIF orientation ------------------------------------------------------
+// Tag 0x0112 of IFD0 of one TIFF structure (the payload of an Exif APP1 after
+// its "Exif\0\0"): 0 = absent, 1..8 / other = its SHORT value (*val), -1 = the
+// host decides (malformed, another type or count, the tag twice)
+static int exif_ifd0_orientation(const uint8_t *t, size_t n, int *val) {
+  if (n < 8) return -1;
+  bool le;
+  if (t[0] == 'I' && t[1] == 'I' && t[2] == 0x2A && t[3] == 0)
+    le = true;
+  else if (t[0] == 'M' && t[1] == 'M' && t[2] == 0 && t[3] == 0x2A)
+    le = false;
+  else
+    return -1;
+  auto u16 = [&](const uint8_t *p) -> uint32_t { return le ? p[0] | (p[1] << 8) : (p[0] << 8) | p[1]; };
+  auto u32 = [&](const uint8_t *p) -> uint32_t { return le ? u16(p) | (u16(p + 2) << 16) : (u16(p) << 16) | u16(p + 2); };
+  const size_t off = u32(t + 4);
+  if (off > n || n - off < 2) return -1;
+  const size_t cnt = u16(t + off);
+  if ((n - off - 2) / 12 < cnt) return -1;
+  int found = 0;
+  for (size_t k = 0; k < cnt; k++) {
+    const uint8_t *e = t + off + 2 + 12 * k;
+    if (u16(e) != 0x0112) continue;
+    if (found++ || u16(e + 2) != 3 || u32(e + 4) != 1) return -1;
+    *val = (int)u16(e + 8);
+  }
+  return found;
+}
+
+// The orientation Pillow's Image.getexif().get(0x0112, 1) yields (markers up to
+// the first SOS: JpegImagePlugin.APP collects them, Image.getexif reads IFD0
+// and falls back to tiff:Orientation of an XMP packet), or FI_EUNSUPPORTED
+// wherever that takes more than an IFD0 lookup -- never another orientation.
+int jpeg_orientation(const uint8_t *d, size_t n, int *orientation) {
+  if (!d || !orientation || n < 2 || d[0] != 0xFF || d[1] != 0xD8) return FI_EINVAL;
+  static const char kExif[] = "Exif\0\0", kXmp[] = "http://ns.adobe.com/xap/1.0/";  // (+ its NUL: 29 bytes)
+  int nexif = 0, found = 0, val = 1;
+  bool xmp = false;
+  size_t p = 2;
+  for (;;) {
+    if (p + 2 > n || d[p] != 0xFF) return FI_EUNSUPPORTED;  // no SOS, or bytes between the segments
+    const int m = d[p + 1];
+    if (m == 0xFF) {  // fill byte
+      p++;
+      continue;
+    }
+    if (m == 0xDA) break;
+    if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) {
+      p += 2;
+      continue;
+    }
+    if (m == 0xD9 || m == 0x00 || p + 4 > n) return FI_EUNSUPPORTED;
+    const size_t L = (size_t)be16(d + p + 2);
+    if (L < 2 || L > n - p - 2) return FI_EUNSUPPORTED;  // the segment runs past the data
+    const uint8_t *s = d + p + 4;
+    const size_t sl = L - 2;
+    if (m == 0xE1 && sl >= 6 && memcmp(s, kExif, 6) == 0) {
+      if (++nexif > 1) return FI_EUNSUPPORTED;  // Pillow concatenates them
+      found = exif_ifd0_orientation(s + 6, sl - 6, &val);
+      if (found < 0) return FI_EUNSUPPORTED;
+    } else if (m == 0xE1 && sl >= 29 && memcmp(s, kXmp, 29) == 0) {
+      xmp = true;
+    }
+    p += 2 + L;
+  }
+  if (!found && xmp) return FI_EUNSUPPORTED;  // tiff:Orientation of the XMP packet applies
+  *orientation = found && val >= 2 && val <= 8 ? val : 1;  // (exif_transpose does nothing for 0, 1, 9..)
+  return FI_OK;
+}
+
 void jpeg_geom(const JpegHdr &H, JpegGeom *G) {
   G->hmax = G->vmax = 1;
   for (int c = 0; c < H.ncomp; c++) {

@@ -63,9 +63,9 @@ int launch_sc_vx(hipStream_t s, int kv, int nch, const ScDesc *descs, const int3
                  const int32_t *ai, const ScParamsDev &P, const uint16_t *skinsat);
 int launch_sc_skinsat(hipStream_t s, uint16_t *table, const ScParamsDev &P);
 int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *len, int n, uint8_t *const *dst,
-                      const int64_t *dst_stride, int out_channels, uint32_t flags, int32_t *status,
-                      void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *), void *actx,
-                      std::string *err);
+                      const int64_t *dst_stride, int out_channels, uint32_t flags, const fi_jpeg_view *views,
+                      int32_t *status, void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *),
+                      void *actx, std::string *err);
 int jpeg_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w, const int32_t *h,
                       const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
                       const int32_t *subsampling, int n, uint8_t *const *out, const size_t *out_cap, size_t *out_len,

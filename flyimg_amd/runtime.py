@@ -81,6 +81,27 @@ def jpeg_info(blob: bytes, progressive: bool = False):
     return (w.value, h.value, c.value) if rc == L.FI_OK else None
 
 
+def jpeg_orientation(blob: bytes):
+    """fi_jpeg_orientation (host only): the EXIF orientation 1..8 that
+    ``ImageOps.exif_transpose`` would apply to this JPEG (1: none); None where
+    the library cannot tell without more than an IFD0 lookup (several Exif
+    segments, XMP, a malformed TIFF structure) or the input is not a JPEG."""
+    o = ctypes.c_int32()
+    rc = L.lib().fi_jpeg_orientation(blob, len(blob), ctypes.byref(o))
+    return o.value if rc == L.FI_OK else None
+
+
+def jpeg_view_dims(w: int, h: int, view):
+    """(w, h) of what a (orientation 1..8, x, y, w, h) view of a w x h source
+    decodes to; ``view`` None: the source's."""
+    if view is None:
+        return w, h
+    o, _, _, vw, vh = view
+    if vw or vh:
+        return vw, vh
+    return (h, w) if o >= 5 else (w, h)
+
+
 def jpeg_scan_info(blob: bytes):
     """(width, height, channels, nscans, nlevels) of a JPEG the GPU decoder
     handles with FI_JPEG_PROGRESSIVE (fi_jpeg_info_ex: a baseline stream is one
@@ -311,13 +332,17 @@ class Context:
         return out
 
     def jpeg_decode(self, blobs: list[bytes], dptrs: list[int], strides: list[int], channels: int = 0,
-                    progressive: bool = False) -> list[int]:
+                    progressive: bool = False, views=None) -> list[int]:
         """fi_jpeg_decode_device: decodes baseline JPEG byte strings (with
         ``progressive=True``, fi_jpeg_decode_device_ex: progressive ones too) into the
         device buffers ``dptrs`` (HWC rows of ``strides`` bytes; channels as
         jpeg_info says, or 3 for every image with ``channels=3``: gray
         replicated); returns the per-image status (0 = decoded,
-        FI_EUNSUPPORTED = decode that one on the host)."""
+        FI_EUNSUPPORTED = decode that one on the host).  ``views``
+        (fi_jpeg_decode_device_view): per image None or (orientation, x, y, w,
+        h) -- the EXIF orientation to apply (0: the file's) and a rectangle of
+        the oriented image (all 0: the whole); that buffer receives h rows of w
+        pixels."""
         n = len(blobs)
         bufs = [ctypes.c_char_p(b) for b in blobs]  # the bytes objects' own storage, no copy
         data = (ctypes.c_void_p * n)(*[ctypes.cast(b, ctypes.c_void_p).value for b in bufs])
@@ -325,24 +350,38 @@ class Context:
         dst = (ctypes.c_void_p * n)(*dptrs)
         st = (ctypes.c_int64 * n)(*strides)
         status = (ctypes.c_int32 * n)()
-        if progressive:
-            rc = self._lib.fi_jpeg_decode_device_ex(self.h, data, lens, n, dst, st, channels, L.FI_JPEG_PROGRESSIVE,
-                                                    status)
+        flags = L.FI_JPEG_PROGRESSIVE if progressive else 0
+        if views is not None and any(v is not None for v in views):
+            va = (L.FiJpegView * n)(*[L.FiJpegView(*(v if v is not None else (1, 0, 0, 0, 0))) for v in views])
+            rc = self._lib.fi_jpeg_decode_device_view(self.h, data, lens, n, dst, st, channels, flags, va, status)
+        elif progressive:
+            rc = self._lib.fi_jpeg_decode_device_ex(self.h, data, lens, n, dst, st, channels, flags, status)
         else:
             rc = self._lib.fi_jpeg_decode_device(self.h, data, lens, n, dst, st, channels, status)
         if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL):
             L.check(rc)
         return list(status)
 
-    def jpeg_decode_host(self, blobs: list[bytes], progressive: bool = False) -> list[np.ndarray | None]:
+    def jpeg_decode_host(self, blobs: list[bytes], progressive: bool = False, views=None) -> list[np.ndarray | None]:
         """jpeg_decode into scratch device buffers, copied back (tests / tools):
         HWC uint8 arrays (H, W, 3) or (H, W) for gray; None where the GPU
-        decoder returned a non-zero status."""
+        decoder returned a non-zero status.  With ``views`` each buffer has its
+        view's size (orientation 0: the file's, read with jpeg_orientation)."""
         infos = [jpeg_info(b, progressive) for b in blobs]
+        if views is not None:
+            dims = []
+            for b, i, v in zip(blobs, infos, views):
+                if i and v is not None and v[0] == 0:
+                    o = jpeg_orientation(b)
+                    v = (o,) + tuple(v[1:]) if o else None
+                    i = i if o else None
+                dims.append(jpeg_view_dims(i[0], i[1], v) + (i[2],) if i else None)
+            infos = dims
         sizes = [(i[0] * i[1] * i[2]) if i else 1 for i in infos]
         ptrs = [self.malloc(max(sz, 1)) for sz in sizes]
         try:
-            status = self.jpeg_decode(blobs, ptrs, [(i[0] * i[2]) if i else 1 for i in infos], progressive=progressive)
+            status = self.jpeg_decode(blobs, ptrs, [(i[0] * i[2]) if i else 1 for i in infos], progressive=progressive,
+                                      views=views)
             out = []
             for info, p, sz, s in zip(infos, ptrs, sizes, status):
                 if s != 0 or not info:

@@ -336,6 +336,36 @@ int fi_jpeg_info_ex(const uint8_t *data, size_t len, uint32_t flags, int32_t *w,
 int fi_jpeg_decode_device_ex(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
                              uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,
                              uint32_t flags, int32_t *status);
+/* Views, opt-in: `-auto-orient` (ImageProcessor.php:78) and ExtractProcessor's
+ * `-crop` applied by the decoder's colour stage, so an EXIF-rotated source or
+ * an extract never exists unrotated or uncropped in device memory.  A view is
+ * an EXIF orientation (1..8, what Pillow's ImageOps.exif_transpose applies;
+ * 5..8 swap width and height) and a rectangle of the ORIENTED image; dst[i]
+ * receives h rows of w pixels: bytes [0, w * channels) of each row, nothing
+ * else of the buffer.  The pixels are those of the oriented, cropped host
+ * decode, bit for bit (chroma upsampling reads across the rectangle's edge).
+ * fi_jpeg_orientation (host only): the file's EXIF orientation as Pillow
+ * 12.2's Image.getexif reads it, 1 when there is none; FI_EUNSUPPORTED where
+ * Pillow's answer takes more than an IFD0 lookup (several Exif segments, an
+ * XMP packet without an EXIF orientation, a tag of another type or count, a
+ * malformed TIFF structure): decide on the host; FI_EINVAL without SOI.
+ * fi_jpeg_decode_device_view: fi_jpeg_decode_device_ex with views[i] per
+ * image (views NULL: exactly fi_jpeg_decode_device_ex, which ignores EXIF, as
+ * does an image whose view is {1, 0, 0, 0, 0}).  Per image: orientation 0 on a
+ * file fi_jpeg_orientation cannot tell is FI_EUNSUPPORTED; an orientation
+ * outside 0..8, a negative origin, a non-positive size other than the
+ * all-zero form, or a rectangle reaching outside the oriented image is
+ * FI_EINVAL; the rest of the batch decodes.  Kernel time of the viewed images'
+ * colour stage: "k_jpeg_color_view" in fi_kernel_stats (the others':
+ * "k_jpeg_color"). */
+typedef struct fi_jpeg_view {
+  int32_t orientation;   /* 1..8: apply this EXIF orientation; 0: read it from the file */
+  int32_t x, y, w, h;    /* rectangle of the oriented image; all 0: the whole image */
+} fi_jpeg_view;
+int fi_jpeg_orientation(const uint8_t *data, size_t len, int32_t *orientation);
+int fi_jpeg_decode_device_view(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
+                               uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,
+                               uint32_t flags, const fi_jpeg_view *views, int32_t *status);
 /* Test hook (not a reference interface): the progressive entropy decode on
  * the CPU, through the block procedures the device kernel runs: info =
  * {components, bw[3], bh[3]} (block grid of each component), qt = each

@@ -37,6 +37,10 @@ typedef struct fi_smartcrop_params {
   double skin_threshold;
   double skin_weight;
 } fi_smartcrop_params;
+typedef struct fi_jpeg_view {
+  int32_t orientation;
+  int32_t x, y, w, h;
+} fi_jpeg_view;
 typedef struct fi_ctx fi_ctx;
 int32_t fi_abi_version(void);
 const char *fi_last_error(void);
@@ -55,3 +59,7 @@ int fi_jpeg_info_ex(const uint8_t *data, size_t len, uint32_t flags, int32_t *w,
 int fi_jpeg_decode_device_ex(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
                              uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,
                              uint32_t flags, int32_t *status);
+int fi_jpeg_orientation(const uint8_t *data, size_t len, int32_t *orientation);
+int fi_jpeg_decode_device_view(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
+                               uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,
+                               uint32_t flags, const fi_jpeg_view *views, int32_t *status);

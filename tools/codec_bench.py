@@ -16,7 +16,14 @@ encode stage (median, min, max over the passes), the bytes a batch's outputs
 are as pixels and as files (with gpu_encode the files are what crosses PCIe),
 the size of the restart-marker files against the host encoder's files of the
 same pixels, and -- from one more, event-timed pass -- the three encode
-kernels' fi_kernel_stats times."""
+kernels' fi_kernel_stats times.
+
+--oriented is the A/B of CodecPipeline(gpu_orient=...) alone: the same sources
+with an orientation-6 EXIF segment spliced in, --reps alternating passes with
+the switch off (the host threads decode and rotate them) and on (they join
+the GPU decode batch through fi_jpeg_decode_device_view), and -- from
+event-timed passes -- k_jpeg_color_view on these files beside k_jpeg_color on
+the same files without the segment."""
 import argparse
 import io
 import json
@@ -37,9 +44,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="alternating passes per setting of the --gpu-encode A/B")
     ap.add_argument("--progressive", action="store_true",
                     help="only the A/B of CodecPipeline(gpu_progressive=...) on progressive sources")
+    ap.add_argument("--oriented", action="store_true",
+                    help="only the A/B of CodecPipeline(gpu_orient=...) on orientation-6 sources")
     a = ap.parse_args()
     if a.progressive:
         return progressive_ab(a)
+    if a.oriented:
+        return oriented_ab(a)
     import numpy as np
     from PIL import Image
 
@@ -161,6 +172,89 @@ def progressive_ab(a):
     for k, v in runs.items():
         res["gpu_progressive_" + k] = {"images_per_s": {"median": round(statistics.median(v), 1),
                                                         "min": round(min(v), 1), "max": round(max(v), 1)}}
+    print(json.dumps(res))
+    for p in pipes.values():
+        p.close()
+    ctx.close()
+
+
+def oriented_ab(a):
+    """Orientation-6 1080p sources through CodecPipeline.process with the
+    gpu_orient switch off and on, alternating passes; then one event-timed
+    pass of each colour kernel: k_jpeg_color_view on the rotated files
+    (and on orientation-3 copies, the same kernel without its LDS phase),
+    k_jpeg_color on the same files without the EXIF segment."""
+    import statistics
+    import struct
+
+    from PIL import Image
+
+    from flyimg_amd import codec
+    from flyimg_amd.runtime import Context
+    from flyimg_amd.synth import synth_rgb
+
+    # APP1: "Exif\0\0" + little-endian TIFF, IFD0 = {0x0112 SHORT 1: 6}
+    def app1(o):
+        body = b"Exif\x00\x00II*\x00" + struct.pack("<LHHHLHHL", 8, 1, 0x0112, 3, 1, o, 0, 0)
+        return b"\xff\xe1" + struct.pack(">H", len(body) + 2) + body
+
+    plain, rotated, flipped = [], [], []  # no EXIF; orientation 6 (through LDS); orientation 3 (same kernel, no LDS)
+    for i in range(8):
+        b = io.BytesIO()
+        Image.fromarray(synth_rgb(1920, 1080, 100 + i)).save(b, "JPEG", quality=90)
+        blob = b.getvalue()
+        cut = 4 + struct.unpack(">H", blob[4:6])[0]  # after the JFIF APP0
+        plain.append(blob)
+        rotated.append(blob[:cut] + app1(6) + blob[cut:])
+        flipped.append(blob[:cut] + app1(3) + blob[cut:])
+    ctx = Context(0)
+    pipes = {"off": codec.CodecPipeline(ctx, a.threads), "on": codec.CodecPipeline(ctx, a.threads, gpu_orient=True)}
+
+    def one_pass(pipe, blobs):
+        t0 = time.perf_counter()
+        done, files = 0, None
+        while done < a.images:
+            n = min(a.batch, a.images - done)
+            files, _ = pipe.process([blobs[(done + k) % len(blobs)] for k in range(n)], [a.options] * n)
+            done += n
+        return done / (time.perf_counter() - t0), files
+
+    last, runs = {}, {k: [] for k in pipes}
+    for p in pipes.values():
+        one_pass(p, rotated)  # warm-up
+    for _ in range(a.reps):
+        for k, p in pipes.items():
+            ips, last[k] = one_pass(p, rotated)
+            runs[k].append(ips)
+    res = {"images": a.images, "batch": a.batch, "threads": a.threads, "options": a.options, "reps": a.reps,
+           "sources": "1920x1080 q90 4:2:0 (Pillow), EXIF orientation 6", "same_output_bytes": last["on"] == last["off"],
+           "decode_stats_on": dict(pipes["on"].decode_stats), "decode_stats_off": dict(pipes["off"].decode_stats)}
+    for k, v in runs.items():
+        res["gpu_orient_" + k] = {"images_per_s": {"median": round(statistics.median(v), 1),
+                                                   "min": round(min(v), 1), "max": round(max(v), 1)}}
+    # the colour kernels, event-timed: a warm pass, then --reps timed passes of each
+    ctx.set_timing(1)
+    kern = {}
+    for key, name, blobs in (("k_jpeg_color_view", "k_jpeg_color_view", rotated),
+                             ("k_jpeg_color_view_orientation_3", "k_jpeg_color_view", flipped),
+                             ("k_jpeg_color", "k_jpeg_color", plain)):
+        one_pass(pipes["on"], blobs)
+        ms = []
+        for _ in range(a.reps):
+            ctx.reset_stats()
+            one_pass(pipes["on"], blobs)
+            t, launches, _ = ctx.stats(name)
+            ms.append(t)
+        kern[key] = {"ms_per_pass": {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3),
+                                      "max": round(max(ms), 3)}, "launches_per_pass": launches}
+    ctx.set_timing(0)
+    ctx.reset_stats()
+    res["kernel"] = kern
+    # orientation 6 over orientation 3: what the transposing path (the LDS phase and its barrier) costs
+    res["rotate_over_flip"] = round(kern["k_jpeg_color_view"]["ms_per_pass"]["median"] /
+                                    max(kern["k_jpeg_color_view_orientation_3"]["ms_per_pass"]["median"], 1e-9), 3)
+    res["view_over_plain"] = round(kern["k_jpeg_color_view"]["ms_per_pass"]["median"] /
+                                   max(kern["k_jpeg_color"]["ms_per_pass"]["median"], 1e-9), 3)
     print(json.dumps(res))
     for p in pipes.values():
         p.close()
