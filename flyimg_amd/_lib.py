@@ -208,6 +208,8 @@ def lib():
                                            ctypes.c_size_t]
     L.fi_jpeg_encode_bound.argtypes = [i32, i32, i32, i32, i32, P(ctypes.c_size_t)]
     L.fi_jpeg_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.fi_png_encode_bound.argtypes = [i32, i32, i32, P(ctypes.c_size_t)]
+    L.fi_png_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -16,7 +16,10 @@ ImageHandler::processNewImage end to end for a batch of encoded images.
            MI355X instead (fi_jpeg_encode_device): the outputs stay in device
            memory and leave it compressed -- the same baseline coding with
            one restart interval per MCU row, byte for byte what
-           libjpeg-turbo writes with ``restart_marker_rows=1``.
+           libjpeg-turbo writes with ``restart_marker_rows=1``.  With
+           ``gpu_png`` on top the alpha outputs are written there as well
+           (fi_png_encode_device): PNG files of the same pixels, deflated
+           per 32 KiB band on the device.
 
 Gray (L), bilevel and palette sources are expanded to RGB / RGBA before the
 GPU (IM would keep a gray JPEG gray: the channels are equal either way), and
@@ -147,7 +150,10 @@ class CodecPipeline:
     default: the files carry restart markers, so their bytes differ from the
     host encoder's, the decoded pixels do not) ``process`` keeps the outputs
     on the device and writes every JPEG there with one fi_jpeg_encode_device
-    call; outputs with alpha still go through the host PNG writer.  With
+    call; outputs with alpha still go through the host PNG writer unless
+    ``gpu_png`` (off by default, needs ``gpu_encode``) sends them through one
+    fi_png_encode_device call per batch: other bytes than the host writer's
+    file, the same decoded pixels.  With
     ``gpu_progressive`` (off by default) progressive JPEG sources join the GPU
     decode batch instead of the host threads (same pixels).  A progressive
     scan is one serial chain on the GPU: measured on 1080p sources the GPU
@@ -162,13 +168,16 @@ class CodecPipeline:
     side."""
 
     def __init__(self, ctx, threads: int = 16, gpu_decode: bool = True, gpu_encode: bool = False,
-                 gpu_progressive: bool = False, gpu_orient: bool = False):
+                 gpu_progressive: bool = False, gpu_orient: bool = False, gpu_png: bool = False):
+        if gpu_png and not gpu_encode:
+            raise ValueError("gpu_png needs gpu_encode=True: the PNG outputs are written by the GPU encode stage")
         self.ctx = ctx
         self.pool = ThreadPoolExecutor(max_workers=max(1, threads))
         self.gpu_decode = gpu_decode
         self.gpu_encode = gpu_encode
         self.gpu_progressive = gpu_progressive
         self.gpu_orient = gpu_orient
+        self.gpu_png = gpu_png
         self.decode_stats = {"gpu": 0, "host": 0}  # images ``process`` decoded on the GPU / on the host
         # ``process``: host seconds in the encode stage, the bytes its outputs
         # were as pixels and are as files (with gpu_encode, what crosses PCIe)
@@ -236,15 +245,17 @@ class CodecPipeline:
     def _gpu_encode(self, outs, quality, held):
         """Every JPEG output in one fi_jpeg_encode_device call: device views
         as they are, host arrays (host-decoded sources) uploaded first; chroma
-        as ``encode``: q >= 90 -> 4:4:4, else 4:2:0.  Alpha outputs: host PNG."""
+        as ``encode``: q >= 90 -> 4:4:4, else 4:2:0.  Alpha outputs: host PNG,
+        or with ``gpu_png`` one fi_png_encode_device call for all of them."""
         encoded = [None] * len(outs)
         views, idx = [], []
+        png_views, png_idx = [], []
         for i, o in enumerate(outs):
             if isinstance(o, tuple):  # a device batch's output (RGB sources: 1 or 3 channels)
                 view = o
             else:
                 ch = o.shape[2] if o.ndim == 3 else 1
-                if ch in (2, 4):
+                if ch in (2, 4) and not self.gpu_png:
                     encoded[i] = encode(o, quality[i])
                     continue
                 o = np.ascontiguousarray(o)
@@ -252,8 +263,18 @@ class CodecPipeline:
                 held.append(p)
                 self.ctx.h2d(p, o)
                 view = (p, o.shape[1], o.shape[0], o.shape[1] * ch, ch)
+                if ch in (2, 4):
+                    png_views.append(view)
+                    png_idx.append(i)
+                    continue
             views.append(view)
             idx.append(i)
+        for i, f in zip(png_idx, self.ctx.png_encode(png_views)):
+            if f is None:
+                msg = L.lib().fi_last_error()
+                raise ExecFailedException("Command failed.\nThe exit code: %d\n%s" % (
+                    L.FI_EINVAL, msg.decode() if msg else f"image {i}: PNG encode"))
+            encoded[i] = f
         qs = [int(quality[i]) for i in idx]
         files = self.ctx.jpeg_encode(views, qs, [0 if q >= 90 else 2 for q in qs])
         for i, f in zip(idx, files):

@@ -1,8 +1,9 @@
-// fi_jpeg_api.cpp -- the GPU JPEG decode / encode entry points of the runtime
-// (fi_runtime.h; the codecs are fi_jpeg.hip, fi_jpeg_enc.hip and their host parsers).
+// fi_jpeg_api.cpp -- the GPU JPEG decode / encode and PNG encode entry points of the runtime
+// (fi_runtime.h; the codecs are fi_jpeg.hip, fi_jpeg_enc.hip, fi_png_enc.hip and their host halves).
 #include "fi_runtime.h"
 #include "fi_jpeg.h"
 #include "fi_jpeg_enc.h"
+#include "fi_png_enc.h"
 
 using namespace fi;
 
@@ -143,6 +144,38 @@ int fi_jpeg_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w
                      status[i] == FI_EUNSUPPORTED ? "channel count or subsampling the GPU JPEG encoder does not write"
                      : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
                                                   : "bad JPEG source, dimensions or quality");
+  return FI_OK;
+}
+// GPU PNG encode (fi_png_enc.hip): the outputs JPEG cannot carry (alpha); the
+// JPEG encoder's scratch, staging and timing plumbing
+int fi_png_encode_bound(int32_t w, int32_t h, int32_t channels, size_t *bytes) {
+  if (!bytes) return set_err(FI_EINVAL, "bad arguments");
+  const int rc = png_enc_bound(w, h, channels, bytes);
+  if (rc)
+    return set_err(rc, rc == FI_EUNSUPPORTED ? "filtered stream beyond 2^31 - 1 bytes" : "bad PNG dimensions or channels");
+  return FI_OK;
+}
+int fi_png_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                         const int32_t *channels, const int64_t *src_stride, const int32_t *filter, int32_t n,
+                         uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status) {
+  if (!c || n < 0 || (n > 0 && (!src || !w || !h || !channels || !src_stride || !out || !out_cap || !out_len || !status)))
+    return set_err(FI_EINVAL, "bad arguments");
+  if (n == 0) return FI_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
+  std::string err;
+  const int rc = png_encode_batch(c->stream, src, w, h, channels, src_stride, filter, n, out, out_cap, out_len, status,
+                                  jpeg_enc_alloc, jpeg_enc_stage, c, &err);
+  jpeg_enc_stage(c, nullptr);
+  collect_timers(c);
+  if (rc) return set_err(rc, "%s", err.c_str());
+  for (int i = 0; i < n; i++)  // the others are encoded
+    if (status[i])
+      return set_err(status[i], "image %d: %s", i,
+                     status[i] == FI_EUNSUPPORTED ? "filtered stream beyond 2^31 - 1 bytes"
+                     : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
+                                                  : "bad PNG source, dimensions, channels or filter");
   return FI_OK;
 }
 

@@ -71,6 +71,11 @@ int jpeg_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
                       const int32_t *subsampling, int n, uint8_t *const *out, const size_t *out_cap, size_t *out_len,
                       int32_t *status, void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *),
                       void *actx, std::string *err);
+int png_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                     const int32_t *channels, const int64_t *src_stride, const int32_t *filter, int n,
+                     uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status,
+                     void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *), void *actx,
+                     std::string *err);
 int launch_sc_score(hipStream_t s, int mode, const ScDesc *descs, int n, size_t lds, const DevCrop *crops,
                     const double *ad, CropScore *scores, ScResult *results, const ScParamsDev &P, const int32_t *ai);
 int launch_sc_score3(hipStream_t s, const ScDesc *descs, int n, size_t lds, const DevCrop *crops, const ScGroup *groups,
@@ -311,7 +316,7 @@ struct fi_ctx {
   DevBuf jpeg[3];           // GPU JPEG decode: upload (compressed data + tables), -, coefficients + planes
   void *jpeg_host = nullptr;  // its pinned staging
   size_t jpeg_host_cap = 0;
-  DevBuf jpeg_enc[3];       // GPU JPEG encode: upload (tables + headers), coefficients + slots, packed streams
+  DevBuf jpeg_enc[3];       // GPU JPEG / PNG encode: upload (tables + headers), coefficients + slots, packed streams
   void *jpeg_enc_host = nullptr;  // its pinned staging (upload, then download)
   size_t jpeg_enc_host_cap = 0;
   struct Timer *jpeg_enc_timer = nullptr;  // the encode kernel being timed (fi_jpeg_encode_device)

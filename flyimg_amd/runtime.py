@@ -147,6 +147,15 @@ def jpeg_encode_bound(w: int, h: int, channels: int, quality: int, subsampling: 
     return n.value
 
 
+def png_encode_bound(w: int, h: int, channels: int) -> int:
+    """fi_png_encode_bound: the true upper bound of the GPU PNG encoder's file
+    size for any image of this geometry (host only); raises FiError for
+    arguments the encoder turns down."""
+    n = ctypes.c_size_t()
+    L.check(L.lib().fi_png_encode_bound(w, h, channels, ctypes.byref(n)))
+    return n.value
+
+
 class Context:
     def __init__(self, device: int = 0):
         self._lib = L.lib()
@@ -447,9 +456,9 @@ class Context:
         ss = list(subsampling) if isinstance(subsampling, (list, tuple)) else [subsampling] * n
         caps = [min(self._jpeg_bound(v, q, s), v[1] * v[2] * v[4] + 1024) for v, q, s in zip(views, qs, ss)]
         offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
-        pool = getattr(self, "_jpeg_out", None)
+        pool = getattr(self, "_enc_out", None)  # the output pool of jpeg_encode and png_encode alike
         if pool is None or pool.size < int(offs[-1]):  # kept: fresh pages are the cost of a large buffer
-            pool = self._jpeg_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
+            pool = self._enc_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
         base = pool.ctypes.data
         rc, status, lens = self._jpeg_encode_call(views, qs, ss, [base + int(o) for o in offs[:-1]], caps)
         if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL) and not (rc == L.FI_ENOMEM and rc in status):
@@ -479,6 +488,77 @@ class Context:
                 c = a.shape[2] if a.ndim == 3 else 1
                 views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
             return self.jpeg_encode(views, quality, subsampling)
+        finally:
+            for p in ptrs:
+                self.free(p)
+
+    def _png_encode_call(self, views, fs, ptrs, caps):
+        n = len(views)
+        I32, I64, SZ, VP = ctypes.c_int32 * n, ctypes.c_int64 * n, ctypes.c_size_t * n, ctypes.c_void_p * n
+        out_len, status = SZ(), I32()
+        rc = self._lib.fi_png_encode_device(
+            self.h, VP(*[v[0] for v in views]), I32(*[v[1] for v in views]), I32(*[v[2] for v in views]),
+            I32(*[v[4] for v in views]), I64(*[v[3] for v in views]), I32(*fs) if fs is not None else None, n,
+            VP(*ptrs), SZ(*caps), out_len, status)
+        return rc, list(status), list(out_len)
+
+    def _png_bound(self, view):
+        b = ctypes.c_size_t()
+        return b.value if self._lib.fi_png_encode_bound(view[1], view[2], view[4], ctypes.byref(b)) == L.FI_OK else 1
+
+    def png_encode_raw(self, views, filter=-1, caps=None):
+        """fi_png_encode_device on (device pointer, w, h, stride, channels)
+        views; ``filter`` per image, one value for all, or None (the NULL
+        pointer: adaptive); ``caps``: output capacities (default:
+        fi_png_encode_bound, 1 where the bound turns the image down).  Returns
+        (rc, status list, length list, output buffer list) with the 0xA5
+        guards of jpeg_encode_raw."""
+        n = len(views)
+        fs = None if filter is None else list(filter) if isinstance(filter, (list, tuple)) else [filter] * n
+        if caps is None:
+            caps = [self._png_bound(v) for v in views]
+        offs = np.concatenate([[0], np.cumsum([c + 64 for c in caps])]).astype(np.int64)
+        pool = np.empty(int(offs[-1]), np.uint8)
+        bufs = [pool[int(offs[i]):int(offs[i + 1])] for i in range(n)]
+        for b, c in zip(bufs, caps):
+            b[max(0, c - 64):] = 0xA5
+        rc, status, lens = self._png_encode_call(views, fs, [b.ctypes.data for b in bufs], caps)
+        return rc, status, lens, bufs
+
+    def png_encode(self, views, filter=-1) -> list[bytes | None]:
+        """fi_png_encode_device: PNG files of device-resident images given as
+        (device pointer, w, h, stride, channels) views, 1..4 channels; any
+        PNG decoder returns the pixels bit for bit.  ``filter``: -1 adaptive,
+        0..4 fixed (per image or one value).  None where the encoder turned the
+        image down.  The output buffers are sized to fi_png_encode_bound (a
+        few hundred bytes above the pixels), so one call always suffices."""
+        n = len(views)
+        if not n:
+            return []
+        fs = list(filter) if isinstance(filter, (list, tuple)) else [filter] * n
+        caps = [self._png_bound(v) for v in views]
+        offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+        pool = getattr(self, "_enc_out", None)  # the output pool of jpeg_encode and png_encode alike
+        if pool is None or pool.size < int(offs[-1]):  # kept: fresh pages are the cost of a large buffer
+            pool = self._enc_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
+        base = pool.ctypes.data
+        rc, status, lens = self._png_encode_call(views, fs, [base + int(o) for o in offs[:-1]], caps)
+        if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL):
+            L.check(rc)  # a failure of the call, not of an image
+        return [pool[int(offs[i]):int(offs[i]) + lens[i]].tobytes() if status[i] == L.FI_OK else None for i in range(n)]
+
+    def png_encode_host(self, images: list[np.ndarray], filter=-1) -> list[bytes | None]:
+        """png_encode of host arrays (HW, HWC with 1..4 channels), uploaded to
+        scratch device buffers first (tests / tools)."""
+        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        ptrs = [self.malloc(max(a.nbytes, 1)) for a in arrs]
+        try:
+            views = []
+            for a, p in zip(arrs, ptrs):
+                self.h2d(p, a)
+                c = a.shape[2] if a.ndim == 3 else 1
+                views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
+            return self.png_encode(views, filter)
         finally:
             for p in ptrs:
                 self.free(p)

@@ -387,7 +387,7 @@ int fi_debug_jpeg_coefs_host(const uint8_t *data, size_t len, uint32_t flags, in
  * rows, 1 or 3 channels, any src_stride[i] >= w * channels, no alignment
  * assumed: fi_process_batch_device outputs go in as they are) into the host
  * buffers out[i] of out_cap[i] bytes and waits; out_len[i] = the encoded
- * size.  status[i]: FI_EUNSUPPORTED for 2 or 4 channels (alpha: write PNG) or
+ * size.  status[i]: FI_EUNSUPPORTED for 2 or 4 channels (alpha: fi_png_encode_device) or
  * another subsampling, FI_EINVAL for quality outside 1..100 or a side outside
  * 1..65535, FI_ENOMEM when out_cap[i] < out_len[i] (nothing is written past
  * out_cap[i]; out_len[i] is the size needed).  Returns the first failing
@@ -399,6 +399,35 @@ int fi_jpeg_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t 
                           const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
                           const int32_t *subsampling, int32_t n, uint8_t *const *out, const size_t *out_cap,
                           size_t *out_len, int32_t *status);
+/* GPU PNG encode: the outputs JPEG cannot carry (2 or 4 channels: alpha) leave
+ * the device as PNG files -- signature, IHDR (bit depth 8, colour type 0 / 4 /
+ * 2 / 6 for 1 / 2 / 3 / 4 channels, no interlace), IDAT chunks, IEND, no
+ * ancillary chunks.  The filtered stream (h rows of a filter-type byte + w *
+ * channels bytes) is cut into bands of 32768 bytes; each band is deflated on
+ * its own (greedy LZ77 inside the band; dynamic Huffman codes, the fixed codes
+ * or stored blocks, whichever is smallest) into its own IDAT chunk; one zlib stream
+ * (32 KiB window) runs across the chunks.  Lossless: any conforming decoder
+ * returns the source pixels.
+ * fi_png_encode_bound (host only): a true upper bound of the file size of any
+ * w x h image -- every band stored: 51 bytes + the filtered stream + 17 bytes
+ * per band; callers size buffers to it.
+ * fi_png_encode_device: encodes n device-resident images src[i] (HWC u8 rows,
+ * 1..4 channels, any src_stride[i] >= w * channels, no alignment assumed) into
+ * the host buffers out[i] of out_cap[i] bytes and waits; out_len[i] = the
+ * encoded size.  filter[i]: -1 = per row the filter type (0..4) with the
+ * lowest sum of min(x, 256 - x) over its filtered bytes, ties to the lower
+ * type; 0..4 = that type on every row; filter == NULL: -1 for every image.
+ * status[i]: FI_EINVAL for other channel counts, a side outside 1..65535 or a
+ * bad filter value, FI_EUNSUPPORTED when the filtered stream h * (w * channels
+ * + 1) exceeds 2^31 - 1 bytes, FI_ENOMEM when out_cap[i] < out_len[i] (nothing
+ * is written past out_cap[i]; out_len[i] is the size needed).  Returns the
+ * first failing status; the other images are encoded.  Kernel times:
+ * "k_png_filter", "k_png_lz", "k_png_codes", "k_png_emit", "k_png_pack" in
+ * fi_kernel_stats (fi_set_timing(1)). */
+int fi_png_encode_bound(int32_t w, int32_t h, int32_t channels, size_t *bytes);
+int fi_png_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                         const int32_t *channels, const int64_t *src_stride, const int32_t *filter, int32_t n,
+                         uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status);
 
 /* Test hook (not a reference interface): the skin / saturation table k_sc_fz
  * reads (2^24 entries, index (r << 16) | (g << 8) | b, value skin | sat << 8)

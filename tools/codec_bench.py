@@ -23,7 +23,16 @@ with an orientation-6 EXIF segment spliced in, --reps alternating passes with
 the switch off (the host threads decode and rotate them) and on (they join
 the GPU decode batch through fi_jpeg_decode_device_view), and -- from
 event-timed passes -- k_jpeg_color_view on these files beside k_jpeg_color on
-the same files without the segment."""
+the same files without the segment.
+
+--gpu-png is the A/B of CodecPipeline(gpu_png=...) alone: RGBA PNG sources
+(seeded synth pictures plus an alpha ramp), w_500, --reps alternating passes
+with the outputs written by the host threads' PNG writer and by
+fi_png_encode_device after a warm-up pass of each: images/s, the host seconds
+in the encode stage, the bytes over PCIe per batch, the five kernels'
+fi_kernel_stats times from one more event-timed pass, and the sizes -- the GPU
+files against Pillow's default and compress_level=1 files of the same pixels,
+their IDAT payloads against zlib levels 1 and 6 on the same filtered stream."""
 import argparse
 import io
 import json
@@ -46,7 +55,11 @@ def main():
                     help="only the A/B of CodecPipeline(gpu_progressive=...) on progressive sources")
     ap.add_argument("--oriented", action="store_true",
                     help="only the A/B of CodecPipeline(gpu_orient=...) on orientation-6 sources")
+    ap.add_argument("--gpu-png", action="store_true",
+                    help="only the A/B of CodecPipeline(gpu_png=...) on RGBA PNG sources")
     a = ap.parse_args()
+    if a.gpu_png:
+        return png_ab(a)
     if a.progressive:
         return progressive_ab(a)
     if a.oriented:
@@ -129,6 +142,121 @@ def main():
     print(json.dumps(res))
     pipe.close()
     ctx.close()
+
+
+def png_payload(blob):
+    """(IDAT payload, filtered stream) of a PNG file."""
+    import struct
+    import zlib
+
+    pos, payload = 8, b""
+    while pos < len(blob):
+        n, typ = struct.unpack(">I4s", blob[pos:pos + 8])
+        if typ == b"IDAT":
+            payload += blob[pos + 8:pos + 8 + n]
+        pos += 12 + n
+    return payload, zlib.decompress(payload)
+
+
+def png_sizes(gpu_files, pixels):
+    """Size ratios of the GPU encoder's files of ``pixels`` (summed over them)."""
+    import zlib
+
+    from PIL import Image
+
+    tot = {"gpu_file": 0, "pillow_default": 0, "pillow_level1": 0, "gpu_idat": 0, "zlib1": 0, "zlib6": 0, "stream": 0}
+    for f, px in zip(gpu_files, pixels):
+        payload, stream = png_payload(f)
+        for key, kw in (("pillow_default", {}), ("pillow_level1", {"compress_level": 1})):
+            b = io.BytesIO()
+            Image.fromarray(px).save(b, "PNG", **kw)
+            tot[key] += len(b.getvalue())
+        tot["gpu_file"] += len(f)
+        tot["gpu_idat"] += len(payload)
+        tot["zlib1"] += len(zlib.compress(stream, 1))
+        tot["zlib6"] += len(zlib.compress(stream, 6))
+        tot["stream"] += len(stream)
+    return {"bytes": tot,
+            "file_vs_pillow_default": round(tot["gpu_file"] / tot["pillow_default"], 4),
+            "file_vs_pillow_level1": round(tot["gpu_file"] / tot["pillow_level1"], 4),
+            "idat_vs_zlib1": round(tot["gpu_idat"] / tot["zlib1"], 4),
+            "idat_vs_zlib6": round(tot["gpu_idat"] / tot["zlib6"], 4)}
+
+
+def png_ab(a):
+    import statistics
+
+    import numpy as np
+    from PIL import Image
+
+    from flyimg_amd import codec
+    from flyimg_amd.runtime import Context
+    from flyimg_amd.synth import synth_rgb
+
+    W, H = 1000, 750
+    options = "w_500"
+    alpha = ((np.arange(W)[None, :] + 2 * np.arange(H)[:, None]) * 255 // (W + 2 * H)).astype(np.uint8)
+    blobs = []
+    for i in range(8):
+        b = io.BytesIO()
+        Image.fromarray(np.dstack([synth_rgb(W, H, 300 + i), alpha])).save(b, "PNG", compress_level=1)
+        blobs.append(b.getvalue())
+    ctx = Context(0)
+
+    def spread(v):
+        return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+
+    def one_pass(pipe):
+        pipe.process_stats = {"s_encode": 0.0, "raw_bytes": 0, "encoded_bytes": 0}
+        t0 = time.perf_counter()
+        done, files = 0, None
+        while done < a.images:
+            n = min(a.batch, a.images - done)
+            files, _ = pipe.process([blobs[(done + k) % len(blobs)] for k in range(n)], [options] * n)
+            done += n
+        return done / (time.perf_counter() - t0), dict(pipe.process_stats), files
+
+    pipes = {"host": codec.CodecPipeline(ctx, a.threads),
+             "gpu": codec.CodecPipeline(ctx, a.threads, gpu_encode=True, gpu_png=True)}
+    runs = {k: [] for k in pipes}
+    last = {}
+    for p in pipes.values():  # warm-up: every shape, every scratch buffer at its size
+        one_pass(p)
+    for _ in range(a.reps):
+        for k, p in pipes.items():
+            ips, st, last[k] = one_pass(p)
+            runs[k].append((ips, st))
+    out = {"source": f"{W}x{H} RGBA PNG", "options": options, "batch": a.batch, "threads": a.threads,
+           "images": a.images, "reps": a.reps}
+    nb = (a.images + a.batch - 1) // a.batch
+    for k in pipes:
+        st = runs[k][-1][1]
+        out[k + "_png"] = {"images_per_s": spread([r[0] for r in runs[k]]),
+                           "s_encode": spread([r[1]["s_encode"] for r in runs[k]]),
+                           "raw_bytes_per_batch": st["raw_bytes"] // nb,
+                           "file_bytes_per_batch": st["encoded_bytes"] // nb}
+    # host arm: the pixels come back and the host writes the files; GPU arm: the
+    # host-decoded batch's pixels come back, go up again and the files come back
+    out["pcie_bytes_per_batch"] = {"host_png_d2h_pixels": out["host_png"]["raw_bytes_per_batch"],
+                                   "gpu_png_d2h_pixels_h2d_pixels_d2h_files":
+                                       2 * out["gpu_png"]["raw_bytes_per_batch"] + out["gpu_png"]["file_bytes_per_batch"]}
+    n8 = min(8, len(last["gpu"]))
+    pixels = [codec.decode(f) for f in last["host"][:n8]]
+    assert all(np.array_equal(codec.decode(g), p) for g, p in zip(last["gpu"][:n8], pixels))
+    out["sizes"] = png_sizes(last["gpu"][:n8], pixels)
+    ctx.set_timing(1)
+    ctx.reset_stats()
+    one_pass(pipes["gpu"])
+    out["kernel_ms_per_pass"] = {}
+    for name in ("k_png_filter", "k_png_lz", "k_png_codes", "k_png_emit", "k_png_pack"):
+        ms, launches, _ = ctx.stats(name)
+        out["kernel_ms_per_pass"][name] = {"ms": round(ms, 3), "launches": launches}
+    ctx.set_timing(0)
+    ctx.reset_stats()
+    for p in pipes.values():
+        p.close()
+    ctx.close()
+    print(json.dumps({"gpu_png_ab": out}))
 
 
 def progressive_ab(a):
