@@ -124,9 +124,9 @@ __global__ __launch_bounds__(kHvThreads, 4) void k_rs_hv(const HvDesc *__restric
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const uint32_t a0 = d[3 * j], a1 = d[3 * j + 1], a2 = d[3 * j + 2];
-        w0[j] = __builtin_amdgcn_perm(a2, __builtin_amdgcn_perm(a1, a0, 0x00060300u), 0x05020100u) ^ 0x80808080u;
-        w1[j] = __builtin_amdgcn_perm(a2, __builtin_amdgcn_perm(a1, a0, 0x00070401u), 0x06020100u) ^ 0x80808080u;
-        w2[j] = __builtin_amdgcn_perm(a2, __builtin_amdgcn_perm(a1, a0, 0x00000502u), 0x07040100u) ^ 0x80808080u;
+        w0[j] = deint_rgb4(0, a0, a1, a2);
+        w1[j] = deint_rgb4(1, a0, a1, a2);
+        w2[j] = deint_rgb4(2, a0, a1, a2);
       }
     } else {
 #pragma unroll 1

@@ -134,14 +134,14 @@ struct ScDesc {
 constexpr int kPrepRows = 16;
 constexpr int kVqRows = 14;  // k_sc_vq: analysed rows per workgroup (16 prescaled rows with the edge halo)
 constexpr int kPrepMaxLds = 64 * 1024;
-// k_sc_hx (fi_smartcrop.hip): 16-row blocks of the H stage one wave walks (a
+// k_sc_hx (fi_sc_prep.hip): 16-row blocks of the H stage one wave walks (a
 // tile = image x 4 column blocks x kHxRb row blocks)
 constexpr int kHxRb = 8;
-// k_sc_fz (fi_smartcrop.hip): the fused per-image prescale + maps; LDS =
+// k_sc_fz (fi_sc_prep.hip): the fused per-image prescale + maps; LDS =
 // kFzRing (80) H-stage rows + max(3 source planes of 16 rows, 16 prescaled rows
 // + luma); <= 80 KB keeps two workgroups per CU
 constexpr int kFzMaxLds = 80 * 1024;
-// k_sc_fd (fi_smartcrop.hip): k_sc_fz's passes with the source rows streamed
+// k_sc_fd (fi_sc_prep.hip): k_sc_fz's passes with the source rows streamed
 // by LDS-DMA, one 16-wave workgroup per CU.  LDS: kFdSlots raw blocks of 16
 // source rows (row pitch fd_rp = 16-B rounded W * 3; a slot rounded up to the
 // DMA's 1 KB steps), a tail that the horizontal pass's last window may read
@@ -220,6 +220,13 @@ __host__ __device__ inline int mfma_i8_k(int l, int j) {
   return j < 8 ? 8 * (l >> 4) + j : 32 + 8 * (l >> 4) + (j - 8);
 #endif
 }
+// channel c (0 R, 1 G, 2 B) of 4 interleaved RGB pixels (the 12 bytes of the
+// dwords a0 a1 a2) as one dword of p - 128 bytes: the MFMA kernels' A operands
+__device__ __forceinline__ uint32_t deint_rgb4(int c, uint32_t a0, uint32_t a1, uint32_t a2) {
+  const uint32_t s1 = c == 0 ? 0x00060300u : c == 1 ? 0x00070401u : 0x00000502u;
+  const uint32_t s2 = c == 0 ? 0x05020100u : c == 1 ? 0x06020100u : 0x07040100u;
+  return __builtin_amdgcn_perm(a2, __builtin_amdgcn_perm(a1, a0, s1), s2) ^ 0x80808080u;
+}
 struct MStrip {               // one column strip (fi_plan.h MfmaStrip) placed in the arena
   int32_t x0, x1, b0, nbytes;
   int32_t c_lo, ncols, pitch, nocb, ks;
@@ -228,7 +235,7 @@ struct MStrip {               // one column strip (fi_plan.h MfmaStrip) placed i
   int32_t vpitch;             // k_rs_vm: Q16 plane columns (multiple of 16)
   int32_t frag2;              // k_rs_vr: arena offset of the two-limb fragments (fi_plan.h MfmaH::frag2)
 };
-// k_sc_hmfma (fi_smartcrop.hip): Pillow's horizontal pass as exact integer
+// k_sc_hmfma (fi_sc_prep.hip): Pillow's horizontal pass as exact integer
 // MFMA.  Per 16-column output block b: source window [s0(b), s0(b) + 64 KS),
 // coefficient limbs L0 + 256 L1 + 65536 L2 (signed i8) in fragment order;
 // s0(b) is 8-B aligned (two 8-byte fragment reads), ks <= 2.

@@ -701,12 +701,9 @@ __global__ __launch_bounds__(256) void k_sc_maps(const ScDesc *__restrict__ desc
     const uint32_t L = sc_luma(r, g, b);
     // detect_edge: ImagingFilter3x3; border copies L; < 3x3 images copied
     uint32_t E = L;
-    if (W >= 3 && H >= 3 && x > 0 && y > 0 && x < W - 1 && y < H - 1) {
-      const int v = 4 * (int)L - (int)pre_luma(D, img, stride, C, x, y - 1) -
-                    (int)pre_luma(D, img, stride, C, x, y + 1) - (int)pre_luma(D, img, stride, C, x - 1, y) -
-                    (int)pre_luma(D, img, stride, C, x + 1, y) + 1;
-      E = (uint32_t)(v <= 0 ? 0 : v >= 255 ? 255 : v);
-    }
+    if (sc_edge_interior(x, y, W, H))
+      E = sc_edge_clamp(L, pre_luma(D, img, stride, C, x, y - 1), pre_luma(D, img, stride, C, x, y + 1),
+                        pre_luma(D, img, stride, C, x - 1, y), pre_luma(D, img, stride, C, x + 1, y));
     D.maps[(int64_t)y * W + x] = sc_skin_sat(r, g, b, L, P) | (E << 8);
   }
 }

@@ -1052,7 +1052,7 @@ int plan_sc(int W, int H, int width, int height, const fi_smartcrop_options &o, 
   return FI_OK;
 }
 
-// k_sc_hrows / k_sc_vmaps launch geometry (fi_smartcrop.hip): row chunks and
+// k_sc_hrows / k_sc_vmaps launch geometry (fi_sc_prep.hip): row chunks and
 // the LDS each needs (transposed H coefficients + staged source rows; staged
 // H-stage rows + prescaled rows of an output chunk with its one-row halo).
 // Exact-integer MFMA form of Pillow's horizontal pass (k_sc_hmfma): for each

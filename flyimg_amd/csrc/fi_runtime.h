@@ -47,7 +47,7 @@ __global__ void k_sc_reduce(const ScDesc *, const int32_t *, int);
 __global__ void k_sc_hpass(const ScDesc *, const int32_t *, int, const int32_t *);
 __global__ void k_sc_vpass(const ScDesc *, const int32_t *, int, const int32_t *);
 __global__ void k_sc_maps(const ScDesc *, const int32_t *, int, const ScParamsDev);
-// per-image smartcrop kernels (fi_smartcrop.hip)
+// per-image smartcrop kernels (fi_sc_prep.hip; launch_sc_score* in fi_sc_score.hip, launch_crop_apply in fi_sc_apply.hip)
 int launch_sc_h(hipStream_t s, const ScDesc *descs, int n, int chunks, int lds, const int32_t *ai);
 int launch_sc_v(hipStream_t s, const ScDesc *descs, int n, int chunks, int lds, const int32_t *ai,
                 const ScParamsDev &P);

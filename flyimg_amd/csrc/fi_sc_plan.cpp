@@ -496,7 +496,7 @@ int fi::enqueue_sc(fi_ctx *c, hipStream_t st, uint8_t *ab, const ScLaunches &X, 
                       const double *ad, CropScore *scores, ScResult *results, const ScParamsDev &PD) {
   auto desc = [&](const Launch &L) { return (const ScDesc *)(ab + L.desc_off); };
   auto pre = [&](const Launch &L) { return (const int32_t *)(ab + L.prefix_off); };
-  // the skin / saturation table of this parameter set (k_sc_fz<true>), built
+  // the skin / saturation table of this parameter set (k_sc_fz), built
   // on the stream that reads it, so batches queued before a parameter change
   // have read the old table first
   const uint16_t *skinsat = nullptr;
@@ -654,7 +654,7 @@ static int run_smartcrop(fi_ctx *c, const uint8_t *d_img, int W, int H, int64_t 
 
 extern "C" {
 
-// Test hook: the skin / saturation table of k_sc_fz<true> / k_sc_fd for `params`,
+// Test hook: the skin / saturation table of k_sc_fz / k_sc_fd for `params`,
 // returned in r-major colour order (the device table is in sc_colour_key order)
 int fi_debug_skinsat(fi_ctx *c, const fi_smartcrop_params *params, uint16_t *out) {
   if (!c || !out) return set_err(FI_EINVAL, "bad arguments");

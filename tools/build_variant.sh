@@ -3,8 +3,8 @@
 # first) with one source replaced by SRC compiled with FLAGS.  For A/B runs
 # through FI_LIB_PATH (tools/gpu_abl.sh).  SRC may be a file outside csrc
 # (e.g. a `git show HEAD:...` copy); it is compiled with csrc on the include path.
-#   tools/build_variant.sh base /tmp/head/fi_smartcrop.hip ""
-#   tools/build_variant.sh pair1 flyimg_amd/csrc/fi_smartcrop.hip "-DFI_FZ_PAIR=1"
+#   tools/build_variant.sh base /tmp/head/fi_sc_prep.hip ""
+#   tools/build_variant.sh novert flyimg_amd/csrc/fi_sc_prep.hip "-DFI_FD_ABL=4"
 set -eu
 cd "$(dirname "$0")/.."
 NAME=$1 SRC=$2 FLAGS=${3:-}
