@@ -281,6 +281,9 @@ void fi_destroy(fi_ctx *c) {
   for (DevBuf *b : {&c->arena, &c->work, &c->io, &c->gather, &c->pix, &c->skinsat, &c->jpeg[0], &c->jpeg[1],
                     &c->jpeg[2], &c->jpeg_enc[0], &c->jpeg_enc[1], &c->jpeg_enc[2]})
     if (b->p) (void)hipFree(b->p);
+  // the table heaps (5.5 GiB of device memory a context; a host-only planner context has none)
+  for (fi_ctx::Heap *h : {&c->heap_i, &c->heap_f, &c->heap_d})
+    if (h->p) (void)hipFree(h->p);
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->jpeg_host) (void)hipHostFree(c->jpeg_host);
   if (c->jpeg_enc_host) (void)hipHostFree(c->jpeg_enc_host);

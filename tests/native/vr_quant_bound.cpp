@@ -198,24 +198,60 @@ static bool check(int W, int H, int tw, int th, uint32_t flags, const char *name
       }
     }
   }
-  double worst = 0;
+  double worst = 0, e16 = 0;
   for (int x = 0; x < nx; x++) CHECK(EH[x] >= 0, "%s: output px %d in no strip", name, x);
   const double evmax = *std::max_element(EV.begin(), EV.end());
   for (int x = 0; x < nx; x++) {
     const double dh = A1[x] * (evmax + 1.0) + EH[x] + 1e-6;
     // RGB: Q16 results differ by <= dh + 1; Gray: + Rec709 sum (coefficients sum to 1) + its rounding
     worst = std::max(worst, (dh + 2.0) / 257.0);
+    e16 = std::max(e16, dh + 1.0);
   }
   CHECK(worst < 1.0, "%s: bound %.4f LSB", name, worst);
   g_worst = std::max(g_worst, worst);
   g_tables++;
   if (verbose)
-    printf("  %s: shifts %d / %d, E_V %.2f Q16, bound %.4f LSB (8-bit)\n", name, s, s2, evmax, worst);
+    // E: the RGB Q16 results (before ScaleQuantumToChar) differ by at most this
+    printf("  %s: shifts %d / %d, E_V %.2f Q16, bound %.4f LSB (8-bit), E %.2f Q16\n", name, s, s2, evmax, worst,
+           e16);
   return true;
 }
 
-int main() {
+// argv[1] == "adversarial": only the geometries of tests/_adversarial.py
+int main(int argc, char **argv) {
   const uint32_t T = FI_OP_THUMBNAIL, F = FI_GEOM_FILL, X = FI_OP_EXTENT, S = FI_GEOM_SHRINK_ONLY, R = FI_OP_RESIZE;
+  const bool only_adv = argc > 1 && !strcmp(argv[1], "adversarial");
+  // the geometries tests/test_gpu_adversarial.py runs hostile content on (tests/_adversarial.py
+  // RESAMPLE_CASES, by name; -colorspace Gray and -rotate do not change the tables): the
+  // vertical-first ones take k_rs_vr, E bounds their Q16 results for the boundary-band assertion
+  {
+    struct Adv {
+      const char *name;
+      int W, H, tw, th;
+      uint32_t f;
+      int cls;  // 0 = k_rs_vr, 1 = vertical first outside its class (k_rs_vm), 2 = horizontal first
+    } adv[] = {{"thumb_333x517_w97", 333, 517, 97, 0, T | S, 0},
+               {"thumb_640x480_w320", 640, 480, 320, 0, T | S, 0},
+               {"thumb_400x300_w150", 400, 300, 150, 0, T | S, 0},
+               {"thumb_1200x900_w150_sampled", 1200, 900, 150, 0, T | S, 0},
+               {"resize_1000x702_w640", 1000, 702, 640, 0, R | S, 2},
+               {"resize_640x481_w317", 640, 481, 317, 0, R | S, 2},
+               {"resize_40x23_w30", 40, 23, 30, 0, R | S, 2},
+               {"enlarge_120x90_w300", 120, 90, 300, 0, T, 1},
+               {"enlarge_120x90_w150", 120, 90, 150, 0, T, 0},
+               {"gray_rot90_640x480_200x200", 640, 480, 200, 200, T | F | X, 2},
+               {"gray_rot90_480x640_200x200", 480, 640, 200, 200, T | F | X, 0},
+               {"rot180_333x517_w97", 333, 517, 97, 0, T | S, 0}};
+    for (const Adv &a : adv) {
+      const bool took = check(a.W, a.H, a.tw, a.th, a.f, a.name, true);
+      CHECK(took == (a.cls == 0), "%s: %s k_rs_vr", a.name, took ? "unexpectedly on" : "not on");
+      if (a.cls) printf("  %s: %s (not bounded here)\n", a.name, a.cls == 2 ? "horizontal first" : "k_rs_vm's class");
+    }
+  }
+  if (only_adv) {
+    printf("%s (%d failures)\n", g_fail ? "FAILED" : "OK", g_fail);
+    return g_fail ? 1 : 0;
+  }
   // BASELINE.json configs (cfg4's ops on its size classes below)
   CHECK(check(3000, 2000, 300, 250, T | F | X, "cfg1 3000x2000 w_300,h_250,c_1", true), "cfg1 not on k_rs_vr");
   CHECK(check(1920, 1080, 500, 0, T | S, "cfg2 1920x1080 w_500", true), "cfg2 not on k_rs_vr");
