@@ -22,6 +22,7 @@ FI_EDEVICE = -4
 FI_EUNSUPPORTED = -5
 FI_ECAPACITY = -6
 FI_JPEG_PROGRESSIVE = 1  # fi_jpeg_info_ex / fi_jpeg_decode_device_ex flags
+FI_PNG_META_ORIENT = 1  # fi_png_info meta: a chunk Pillow's exif_transpose could take an orientation from
 
 FI_OP_THUMBNAIL = 1 << 0
 FI_OP_RESIZE = 1 << 1
@@ -210,6 +211,8 @@ def lib():
     L.fi_jpeg_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.fi_png_encode_bound.argtypes = [i32, i32, i32, P(ctypes.c_size_t)]
     L.fi_png_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.fi_png_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(i32), P(i32), P(i32), P(i32), P(i32)]
+    L.fi_png_decode_device.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     _lib = L
     return L
 

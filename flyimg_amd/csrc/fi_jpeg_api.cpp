@@ -1,9 +1,10 @@
-// fi_jpeg_api.cpp -- the GPU JPEG decode / encode and PNG encode entry points of the runtime
-// (fi_runtime.h; the codecs are fi_jpeg.hip, fi_jpeg_enc.hip, fi_png_enc.hip and their host halves).
+// fi_jpeg_api.cpp -- the GPU JPEG decode / encode and PNG encode / decode entry points of the runtime
+// (fi_runtime.h; the codecs are fi_jpeg.hip, fi_jpeg_enc.hip, fi_png_enc.hip, fi_png_dec.hip and their host halves).
 #include "fi_runtime.h"
 #include "fi_jpeg.h"
 #include "fi_jpeg_enc.h"
 #include "fi_png_enc.h"
+#include "fi_png_dec.h"
 
 using namespace fi;
 
@@ -176,6 +177,42 @@ int fi_png_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w,
                      status[i] == FI_EUNSUPPORTED ? "filtered stream beyond 2^31 - 1 bytes"
                      : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
                                                   : "bad PNG source, dimensions, channels or filter");
+  return FI_OK;
+}
+// GPU PNG decode (fi_png_dec.hip): the sources a JPEG cannot be (alpha, palette); the JPEG
+// decoder's scratch, staging and timing plumbing
+int fi_png_info(const uint8_t *data, size_t len, int32_t *w, int32_t *h, int32_t *channels, int32_t *color_type,
+                int32_t *meta) {
+  if (!data || !w || !h || !channels) return set_err(FI_EINVAL, "bad arguments");
+  PngSrc S;
+  const int rc = png_parse(data, len, &S);
+  if (rc) return set_err(rc, rc == FI_EUNSUPPORTED ? "PNG file the GPU decoder does not handle" : "not a PNG file");
+  *w = S.w;
+  *h = S.h;
+  *channels = S.channels;
+  if (color_type) *color_type = S.color_type;
+  if (meta) *meta = S.meta;
+  return FI_OK;
+}
+int fi_png_decode_device(fi_ctx *c, const uint8_t *const *data, const size_t *len, int32_t n, uint8_t *const *dst,
+                         const int64_t *dst_stride, const int32_t *out_channels, int32_t *status) {
+  if (!c || n < 0 || (n > 0 && (!data || !len || !dst || !dst_stride || !status)))
+    return set_err(FI_EINVAL, "bad arguments");
+  if (n == 0) return FI_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
+  std::string err;
+  const int rc = png_decode_batch(c->stream, data, len, n, dst, dst_stride, out_channels, status, jpeg_alloc,
+                                  jpeg_enc_stage, c, &err);
+  jpeg_enc_stage(c, nullptr);
+  collect_timers(c);
+  if (rc) return set_err(rc, "%s", err.c_str());
+  for (int i = 0; i < n; i++)  // the others are decoded; the caller decodes these on the host
+    if (status[i])
+      return set_err(status[i], "image %d: %s", i,
+                     status[i] == FI_EUNSUPPORTED ? "PNG file the GPU decoder does not handle"
+                                                  : "malformed PNG, or out_channels / dst_stride that do not fit it");
   return FI_OK;
 }
 

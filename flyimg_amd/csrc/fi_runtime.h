@@ -76,6 +76,10 @@ int png_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w
                      uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status,
                      void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *), void *actx,
                      std::string *err);
+int png_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *len, int n, uint8_t *const *dst,
+                     const int64_t *dst_stride, const int32_t *out_channels, int32_t *status,
+                     void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *), void *actx,
+                     std::string *err);
 int launch_sc_score(hipStream_t s, int mode, const ScDesc *descs, int n, size_t lds, const DevCrop *crops,
                     const double *ad, CropScore *scores, ScResult *results, const ScParamsDev &P, const int32_t *ai);
 int launch_sc_score3(hipStream_t s, const ScDesc *descs, int n, size_t lds, const DevCrop *crops, const ScGroup *groups,

@@ -156,6 +156,16 @@ def png_encode_bound(w: int, h: int, channels: int) -> int:
     return n.value
 
 
+def png_info(blob: bytes):
+    """fi_png_info: (width, height, channels, colour type, meta) of a PNG file
+    the GPU decoder reproduces exactly (8-bit, non-interlaced; channels = the
+    natural count, a palette counts 3, with tRNS 4; meta: FI_PNG_META_ORIENT
+    when a chunk could carry an orientation), else None: decode on the host."""
+    v = [ctypes.c_int32() for _ in range(5)]
+    rc = L.lib().fi_png_info(blob, len(blob), *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v) if rc == L.FI_OK else None
+
+
 class Context:
     def __init__(self, device: int = 0):
         self._lib = L.lib()
@@ -404,6 +414,54 @@ class Context:
             for p in ptrs:
                 self.free(p)
 
+    def png_decode(self, blobs: list[bytes], dptrs: list[int], strides: list[int], out_channels=None) -> list[int]:
+        """fi_png_decode_device: decodes PNG byte strings into the device
+        buffers ``dptrs`` (HWC rows of ``strides`` bytes).  ``out_channels``:
+        None or 0 = the natural count png_info reports, 3 = RGB (FI_EINVAL for
+        a source with alpha), 4 = RGBA; one value or a list.  Returns the
+        per-image status (0 = decoded, FI_EUNSUPPORTED = decode that one on the
+        host, FI_EINVAL = malformed, or channels / stride that do not fit)."""
+        n = len(blobs)
+        if not n:
+            return []
+        bufs = [ctypes.c_char_p(b) for b in blobs]  # the bytes objects' own storage, no copy
+        data = (ctypes.c_void_p * n)(*[ctypes.cast(b, ctypes.c_void_p).value for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in blobs])
+        dst = (ctypes.c_void_p * n)(*dptrs)
+        st = (ctypes.c_int64 * n)(*strides)
+        status = (ctypes.c_int32 * n)()
+        oc = None
+        if out_channels is not None:
+            oc = (ctypes.c_int32 * n)(*(out_channels if isinstance(out_channels, (list, tuple)) else [out_channels] * n))
+        rc = self._lib.fi_png_decode_device(self.h, data, lens, n, dst, st, oc, status)
+        if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL):
+            L.check(rc)
+        return list(status)
+
+    def png_decode_host(self, blobs: list[bytes], out_channels=None) -> list[np.ndarray | None]:
+        """png_decode into scratch device buffers, copied back (tests / tools):
+        HWC uint8 arrays (H, W, C), (H, W) for one channel; None where the GPU
+        decoder returned a non-zero status."""
+        n = len(blobs)
+        ocs = list(out_channels) if isinstance(out_channels, (list, tuple)) else [out_channels or 0] * n
+        infos = [png_info(b) for b in blobs]
+        dims = [(i[0], i[1], oc or i[2]) if i else None for i, oc in zip(infos, ocs)]
+        ptrs = [self.malloc(max(d[0] * d[1] * d[2], 1) if d else 1) for d in dims]
+        try:
+            status = self.png_decode(blobs, ptrs, [d[0] * d[2] if d else 1 for d in dims], ocs)
+            out = []
+            for d, p, s in zip(dims, ptrs, status):
+                if s != 0 or not d:
+                    out.append(None)
+                    continue
+                w, h, c = d
+                a = self.d2h(p, w * h * c)
+                out.append(a.reshape(h, w) if c == 1 else a.reshape(h, w, c))
+            return out
+        finally:
+            for p in ptrs:
+                self.free(p)
+
     def _jpeg_encode_call(self, views, qs, ss, ptrs, caps):
         n = len(views)
         I32, I64, SZ, VP = ctypes.c_int32 * n, ctypes.c_int64 * n, ctypes.c_size_t * n, ctypes.c_void_p * n
@@ -564,17 +622,20 @@ class Context:
                 self.free(p)
 
     def process_device_resident(self, views, ops: list[Op]):
-        """fi_process_batch_device on device-resident RGB8 sources given as
-        (device pointer, width, height, stride) views (e.g. fi_jpeg_decode_device
-        targets, extract offsets applied), the outputs left on the device (for
+        """fi_process_batch_device on device-resident sources given as (device
+        pointer, width, height, stride) views of RGB8 pixels (e.g. fi_jpeg_decode_device
+        targets, extract offsets applied) or (device pointer, width, height,
+        stride, channels) views (3, or 4: RGBA, e.g. fi_png_decode_device
+        targets), the outputs left on the device (for
         jpeg_encode): (base, out_views, fi_image records, rc); out_views[i] is
         the (device pointer, w, h, stride, channels) view of output i or None,
         inside the allocation ``base``, which the caller frees."""
         n = len(views)
         arr = (L.FiImage * max(n, 1))()
-        for i, ((p, w, h, st), op) in enumerate(zip(views, ops)):
+        for i, (v, op) in enumerate(zip(views, ops)):
             a = arr[i]
-            a.src, a.src_w, a.src_h, a.src_stride, a.src_channels = p, w, h, st, 3
+            p, w, h, st = v[:4]
+            a.src, a.src_w, a.src_h, a.src_stride, a.src_channels = p, w, h, st, v[4] if len(v) > 4 else 3
             _fill(a, op)
         L.lib().fi_plan(arr, n)
         caps = [max(arr[i].out_w * arr[i].out_h * max(arr[i].out_channels, 1), 1) for i in range(n)]

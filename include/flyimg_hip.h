@@ -429,6 +429,44 @@ int fi_png_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t *
                          const int32_t *channels, const int64_t *src_stride, const int32_t *filter, int32_t n,
                          uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status);
 
+/* GPU PNG decode (opt-in): 8-bit, non-interlaced PNG sources of colour type
+ * 0 / 2 / 4 / 6, or 3 with a PLTE and an optional tRNS, decoded into device
+ * memory bit for bit as Pillow reads them: one 64-lane workgroup inflates an
+ * image (a serial chain; the batch supplies the parallelism), a second kernel
+ * checks the Adler-32 and a third undoes the row filters as a wavefront.
+ * fi_png_info (host only): FI_OK only for files the device path reproduces
+ * exactly; channels = the natural count (1 / 2 / 3 / 4 for colour type 0 / 4 /
+ * 2 / 6, palette 3, palette with tRNS 4); color_type and meta may be NULL.
+ * FI_EUNSUPPORTED = decode this one on the host: bit depth 1, 2, 4 or 16, Adam7
+ * interlace, tRNS on colour type 0 or 2, an acTL chunk, a filtered stream h *
+ * (w * c + 1) above 2^31 - 1 bytes, a CRC mismatch on IHDR, PLTE, tRNS, IDAT or
+ * IEND (ancillary chunks are not checked), a zlib header with FDICT or a
+ * method or window zlib would refuse, a missing IEND, bytes after IEND.
+ * FI_EINVAL: no PNG signature or a broken IHDR.  meta gets FI_PNG_META_ORIENT
+ * when the file carries, anywhere, an eXIf chunk or a tEXt / zTXt / iTXt chunk
+ * with the keyword "Raw profile type exif", "Raw profile type APP1" or
+ * "XML:com.adobe.xmp": the library does not interpret them, the caller keeps
+ * such files on the host.
+ * fi_png_decode_device: decodes n files from host memory into the device
+ * buffers dst[i] (HWC rows of dst_stride[i] bytes, no alignment assumed) and
+ * waits.  out_channels[i] (or a NULL array: 0): 0 = the natural count; 3 = RGB,
+ * gray replicated and palette expanded, FI_EINVAL for a source with alpha; 4 =
+ * RGBA, alpha 255 where the source has none.  A palette index beyond PLTE
+ * gives (0, 0, 0) with alpha 255, one beyond tRNS alpha 255 (Pillow's
+ * convert).  status[i]: what fi_png_info says of the file, or FI_EINVAL where
+ * the device finds a corrupt deflate stream (zlib's validity rules), a filter
+ * byte above 4, a stream that does not inflate to exactly h * (w * c + 1) bytes
+ * or an Adler-32 mismatch (the buffer's contents are then undefined).  Returns
+ * the first failing status; the other images are decoded.  Kernel times:
+ * "k_png_inflate", "k_png_adler", "k_png_unfilter" in fi_kernel_stats
+ * (fi_set_timing(1)). */
+#define FI_PNG_META_ORIENT 1   /* a chunk Pillow's exif_transpose could take an orientation from */
+int fi_png_info(const uint8_t *data, size_t len, int32_t *w, int32_t *h,
+                int32_t *channels, int32_t *color_type, int32_t *meta);
+int fi_png_decode_device(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
+                         uint8_t *const *dst, const int64_t *dst_stride,
+                         const int32_t *out_channels, int32_t *status);
+
 /* Test hook (not a reference interface): the skin / saturation table k_sc_fz
  * reads (2^24 entries, index (r << 16) | (g << 8) | b, value skin | sat << 8)
  * built for `params` (NULL: defaults) and copied to out, so a test can compare

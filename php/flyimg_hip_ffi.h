@@ -67,3 +67,8 @@ int fi_png_encode_bound(int32_t w, int32_t h, int32_t channels, size_t *bytes);
 int fi_png_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t *w, const int32_t *h,
                          const int32_t *channels, const int64_t *src_stride, const int32_t *filter, int32_t n,
                          uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status);
+int fi_png_info(const uint8_t *data, size_t len, int32_t *w, int32_t *h,
+                int32_t *channels, int32_t *color_type, int32_t *meta);
+int fi_png_decode_device(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
+                         uint8_t *const *dst, const int64_t *dst_stride,
+                         const int32_t *out_channels, int32_t *status);

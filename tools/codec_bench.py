@@ -32,7 +32,17 @@ fi_png_encode_device after a warm-up pass of each: images/s, the host seconds
 in the encode stage, the bytes over PCIe per batch, the five kernels'
 fi_kernel_stats times from one more event-timed pass, and the sizes -- the GPU
 files against Pillow's default and compress_level=1 files of the same pixels,
-their IDAT payloads against zlib levels 1 and 6 on the same filtered stream."""
+their IDAT payloads against zlib levels 1 and 6 on the same filtered stream.
+
+--gpu-png-decode is the A/B of CodecPipeline(gpu_png_decode=...) on the same
+RGBA PNG sources and request: --reps alternating passes, after a warm-up pass
+of each, of the host-decode arm with gpu_png (the best arm before the device
+decoder), of the device decoder with the host PNG writer, and of the fully
+device-resident arm (gpu_png_decode + gpu_encode + gpu_png); the decode
+kernels' fi_kernel_stats times from --reps event-timed passes; and --sweep, a
+list of batch sizes at which the first and the last arm run one batch per pass
+(an image's inflate is one wave: where the device decoder overtakes --threads
+host threads is a matter of the batch)."""
 import argparse
 import io
 import json
@@ -57,7 +67,12 @@ def main():
                     help="only the A/B of CodecPipeline(gpu_orient=...) on orientation-6 sources")
     ap.add_argument("--gpu-png", action="store_true",
                     help="only the A/B of CodecPipeline(gpu_png=...) on RGBA PNG sources")
+    ap.add_argument("--gpu-png-decode", action="store_true",
+                    help="only the A/B of CodecPipeline(gpu_png_decode=...) on RGBA PNG sources")
+    ap.add_argument("--sweep", default="16,64,256,1024", help="batch sizes of the --gpu-png-decode crossover sweep")
     a = ap.parse_args()
+    if a.gpu_png_decode:
+        return png_decode_ab(a)
     if a.gpu_png:
         return png_ab(a)
     if a.progressive:
@@ -257,6 +272,90 @@ def png_ab(a):
         p.close()
     ctx.close()
     print(json.dumps({"gpu_png_ab": out}))
+
+
+def png_decode_ab(a):
+    import statistics
+
+    import numpy as np
+    from PIL import Image
+
+    from flyimg_amd import codec
+    from flyimg_amd.runtime import Context
+    from flyimg_amd.synth import synth_rgb
+
+    W, H = 1000, 750
+    options = "w_500"
+    alpha = ((np.arange(W)[None, :] + 2 * np.arange(H)[:, None]) * 255 // (W + 2 * H)).astype(np.uint8)
+    blobs = []
+    for i in range(8):  # (the sources of --gpu-png)
+        b = io.BytesIO()
+        Image.fromarray(np.dstack([synth_rgb(W, H, 300 + i), alpha])).save(b, "PNG", compress_level=1)
+        blobs.append(b.getvalue())
+    ctx = Context(0)
+
+    def spread(v, nd=1):
+        return {"median": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+
+    def one_pass(pipe, images, batch):
+        t0 = time.perf_counter()
+        done, files = 0, None
+        while done < images:
+            n = min(batch, images - done)
+            files, _ = pipe.process([blobs[(done + k) % len(blobs)] for k in range(n)], [options] * n)
+            done += n
+        return done / (time.perf_counter() - t0), files
+
+    pipes = {"host_decode_gpu_png": codec.CodecPipeline(ctx, a.threads, gpu_encode=True, gpu_png=True),
+             "gpu_decode_host_png": codec.CodecPipeline(ctx, a.threads, gpu_png_decode=True),
+             "gpu_decode_gpu_png": codec.CodecPipeline(ctx, a.threads, gpu_encode=True, gpu_png=True,
+                                                       gpu_png_decode=True)}
+    runs, last = {k: [] for k in pipes}, {}
+    for p in pipes.values():  # warm-up: every shape, every scratch buffer at its size
+        one_pass(p, a.images, a.batch)
+    for _ in range(a.reps):
+        for k, p in pipes.items():
+            ips, last[k] = one_pass(p, a.images, a.batch)
+            runs[k].append(ips)
+    out = {"source": f"{W}x{H} RGBA PNG (Pillow compress_level=1)", "source_bytes": sum(map(len, blobs)) // len(blobs),
+           "options": options, "batch": a.batch, "threads": a.threads, "images": a.images, "reps": a.reps}
+    for k in pipes:
+        out[k] = {"images_per_s": spread(runs[k]), "decode_stats": dict(pipes[k].decode_stats)}
+    n8 = min(8, a.batch)
+    pixels = [codec.decode(f) for f in last["host_decode_gpu_png"][:n8]]
+    out["same_pixels"] = all(np.array_equal(codec.decode(f), p)
+                             for k in pipes for f, p in zip(last[k][:n8], pixels))
+    # the decode kernels, event-timed: per pass of --images in batches of --batch
+    ctx.set_timing(1)
+    names = ("k_png_inflate", "k_png_adler", "k_png_unfilter")
+    ms = {n: [] for n in names}
+    launches = 0
+    for _ in range(a.reps):
+        ctx.reset_stats()
+        one_pass(pipes["gpu_decode_gpu_png"], a.images, a.batch)
+        for n in names:
+            t, launches, _ = ctx.stats(n)
+            ms[n].append(t)
+    ctx.set_timing(0)
+    ctx.reset_stats()
+    out["kernel_ms_per_pass"] = {n: dict(spread(v, 3), launches=launches) for n, v in ms.items()}
+    # the crossover: one batch of B images per pass
+    sweep = {}
+    for bs in [int(s) for s in a.sweep.split(",") if s]:
+        arms = ("host_decode_gpu_png", "gpu_decode_gpu_png")
+        r = {k: [] for k in arms}
+        for k in arms:
+            one_pass(pipes[k], bs, bs)
+        for _ in range(a.reps):
+            for k in arms:
+                r[k].append(one_pass(pipes[k], bs, bs)[0])
+        sweep[str(bs)] = {k: spread(v) for k, v in r.items()}
+        sweep[str(bs)]["gpu_over_host"] = round(statistics.median(r[arms[1]]) / statistics.median(r[arms[0]]), 3)
+    out["sweep_images_per_s"] = sweep
+    for p in pipes.values():
+        p.close()
+    ctx.close()
+    print(json.dumps({"gpu_png_decode_ab": out}))
 
 
 def progressive_ab(a):
