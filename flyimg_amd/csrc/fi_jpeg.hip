@@ -22,8 +22,13 @@
 //            transposing orientations through LDS.
 //
 // Unsupported streams (progressive, arithmetic, 12-bit, CMYK / Adobe
-// transforms, other samplings, several scans) return FI_EUNSUPPORTED from
-// jpeg_parse so the caller decodes them on the host.
+// transforms, other samplings, several scans, restart markers out of
+// sequence) return FI_EUNSUPPORTED from jpeg_parse so the caller decodes them
+// on the host.  Corrupt entropy data is decoded as libjpeg decodes it (data
+// that runs out: BitReader::short_of_data); where that is not worth restating
+// (coefficients beyond the range in which libjpeg's SIMD IDCT equals
+// jidctint.c, a progressive symbol stored outside its scan's band) a kernel
+// raises the image's handover flag, read back as FI_EUNSUPPORTED.
 //
 // Opt-in (FI_JPEG_PROGRESSIVE): complete Huffman progressive (SOF2) streams.
 //   host     every SOS up to EOI into a scan list (the tables and DRI in force
@@ -66,13 +71,19 @@ typedef __attribute__((address_space(1))) const uint32_t g_u32;
 // read with v_readlane; the next 256 bytes are in flight in `nxt` (their
 // latency hides behind the decode of the current window).  The segment is
 // zero padded by >= 512 bytes.
+// `fake` counts the zero bits supplied after a marker or the end of the data
+// (they sit below the real ones): once nbits < fake a request went beyond the
+// real bits, which is when jdhuff.c sets insufficient_data; fills add to both
+// counts alike, so the condition holds from then on.  libjpeg finishes that
+// MCU from the zero bits and leaves the later MCUs of the interval zero.
 struct BitReader {
   const uint8_t *p;
   uint32_t win, nxt;
   int wbase, pos, end;
   uint64_t buf;
-  int nbits;
+  int nbits, fake;
   bool marker;
+  __device__ __forceinline__ bool short_of_data() const { return nbits < fake; }
   __device__ __forceinline__ void advance_window() {
     if (pos - wbase >= 256) {  // bytes [pos, pos + 4) stay inside win + the first dword of nxt
       win = nxt;
@@ -96,6 +107,7 @@ struct BitReader {
     end = len;
     buf = 0;
     nbits = 0;
+    fake = 0;
     marker = false;
   }
   // jdhuff.c jpeg_fill_bit_buffer: stuffed 0xFF00 -> 0xFF; at a marker (or the
@@ -125,11 +137,14 @@ struct BitReader {
           } else {
             marker = true;
             b = 0;
+            fake += 8;
           }
         } else {
           pos++;
         }
         advance_window();
+      } else {
+        fake += 8;
       }
       buf = (buf << 8) | b;
       nbits += 8;
@@ -153,8 +168,8 @@ __device__ __forceinline__ int jpeg_decode_sym(BitReader &br, const TAB *t) {
     l++;
     code = (int32_t)br.peek(l);
   }
-  if (l > 16) {  // corrupt data: jdhuff.c warns and returns 0
-    br.skip(0);
+  if (l > 16) {  // corrupt data: jdhuff.c warns and returns 0, the 17 bits it tried consumed
+    br.skip(17);
     return 0;
   }
   br.skip(l);
@@ -257,6 +272,23 @@ __global__ __launch_bounds__(64) void k_jpeg_huff(const JpegDesc *__restrict__ d
           }
         }
     }
+    if (!br.short_of_data()) continue;
+    // jdhuff.c insufficient_data: this MCU was finished from zero bits; the
+    // later ones of the interval stay zero (uniform grey)
+    for (int m = mcu + 1; m < I.mcu1; m++) {
+      const int zy = m / mcux, zx = m - zy * mcux;
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        if (c >= ncomp) break;
+        for (int by = 0; by < vs[c]; by++)
+          for (int bx = 0; bx < hs[c]; bx++) {
+            const int row = zy * vs[c] + by, col = zx * hs[c] + bx;
+            if (tid < 8)
+              reinterpret_cast<uint4 *>(work + co[c] + ((int64_t)row * bw[c] + col) * 128)[tid] = uint4{0, 0, 0, 0};
+          }
+      }
+    }
+    break;
   }
 }
 
@@ -288,9 +320,11 @@ struct JpegProgDevOps {
 
 __global__ __launch_bounds__(64) void k_jpeg_prog(const JpegDesc *__restrict__ descs,
                                                   const JpegProgItem *__restrict__ items, int nitems,
-                                                  const JpegHuff *__restrict__ huff, uint8_t *__restrict__ work) {
+                                                  const JpegHuff *__restrict__ huff, uint8_t *__restrict__ work,
+                                                  int32_t *__restrict__ handover) {
   __shared__ JpegHuff sh[3];
   __shared__ __attribute__((aligned(16))) int16_t blk[64];
+  __shared__ int outside;  // set where corrupt data leaves the scan's band (kept out of the registers: rare)
   typedef __attribute__((address_space(3))) const JpegHuff l_huff;
   const int tid = threadIdx.x;
   if ((int)blockIdx.x >= nitems) return;
@@ -303,6 +337,7 @@ __global__ __launch_bounds__(64) void k_jpeg_prog(const JpegDesc *__restrict__ d
     for (int i = tid; i < (int)sizeof(JpegHuff) / 4; i += 64) dstw[i] = src[i];
   }
   blk[tid] = 0;
+  if (tid == 0) outside = 0;
   __syncthreads();
   const JpegDesc *Dp = descs + I.img;
   int hs[3], vs[3], bw[3];
@@ -341,10 +376,15 @@ __global__ __launch_bounds__(64) void k_jpeg_prog(const JpegDesc *__restrict__ d
   JpegProgState S{};
   int16_t *b = blk;
   int k = 0;
+  // corrupt data that makes libjpeg store outside the scan's band (fi_jpeg_prog.h): handover[image] = 1,
+  // and the host decodes that image
   if (!refine) {
     // first pass: the procedure writes the band of the staging block (zero
     // before), the band's lanes store it
     for (int j = 0; j < nblk; j++) {
+      // jdphuff.c insufficient_data: the MCU it was raised in is finished, the later ones are left alone
+      // (an AC scan's MCU is one block)
+      if (br.short_of_data() && (bpm == 1 || j % bpm == 0)) break;
       if (!dc && S.eobrun > 0) {  // the blocks of an end-of-band run stay zero
         const uint32_t left = (uint32_t)(nblk - j), skip = S.eobrun < left ? S.eobrun : left;
         S.eobrun -= skip;
@@ -360,13 +400,14 @@ __global__ __launch_bounds__(64) void k_jpeg_prog(const JpegDesc *__restrict__ d
         else
           jpeg_prog_dc_first<JpegProgDevOps>(br, (l_huff *)(sh + 2), b, S.pred[2], Al);
       } else {
-        jpeg_prog_ac_first<JpegProgDevOps>(br, (l_huff *)(sh + 0), b, S.eobrun, Ss, Se, Al);
+        if (!jpeg_prog_ac_first<JpegProgDevOps>(br, (l_huff *)(sh + 0), b, S.eobrun, Ss, Se, Al)) outside = 1;
       }
       if (mine) {
         g[tid] = b[tid];
         b[tid] = 0;
       }
     }
+    if (outside && tid == 0) handover[items[blockIdx.x].img] = 1;
     return;
   }
   // refinement: lane z holds coefficient z of the block (the next block's is
@@ -374,6 +415,7 @@ __global__ __launch_bounds__(64) void k_jpeg_prog(const JpegDesc *__restrict__ d
   int16_t pre = 0;
   if (mine && nblk > 0) pre = w16[locate(0, k) + tid];
   for (int j = 0; j < nblk; j++) {
+    if (br.short_of_data() && (bpm == 1 || j % bpm == 0)) break;  // (a DC refinement reads zeros: no change)
     int16_t *g = w16 + locate(j, k);
     const int16_t cur = pre;
     if (mine && j + 1 < nblk) {
@@ -387,11 +429,12 @@ __global__ __launch_bounds__(64) void k_jpeg_prog(const JpegDesc *__restrict__ d
       JpegProgRefine R{};
       R.nz = __ballot(mine && cur != 0);
       R.has = __ballot(mine && (cur & (1 << Al)) != 0);
-      jpeg_prog_ac_refine<JpegProgDevOps>(br, (l_huff *)(sh + 0), R, S.eobrun, Ss, Se);
+      if (!jpeg_prog_ac_refine<JpegProgDevOps>(br, (l_huff *)(sh + 0), R, S.eobrun, Ss, Se)) outside = 1;
       out = jpeg_prog_refined(cur, tid, R, Al);
     }
     if (mine && out != cur) g[tid] = out;
   }
+  if (outside && tid == 0) handover[items[blockIdx.x].img] = 1;
 }
 
 // ---------------------------------------------------------------------------
@@ -407,17 +450,18 @@ __device__ __forceinline__ uint8_t jpeg_range_limit(int x) {  // IDCT_range_limi
 // (image, component) pair (3 pairs per image, empty ones for gray), blk0[3 n] = total
 __device__ __forceinline__ void jpeg_idct_block(const JpegDesc *__restrict__ descs, const int64_t *__restrict__ blk0,
                                                 int nimg, const uint16_t *__restrict__ qts, uint8_t *__restrict__ work,
-                                                int64_t i);
+                                                int32_t *__restrict__ handover, int64_t i);
 // (grid-stride, as k_jpeg_color)
 __global__ __launch_bounds__(256) void k_jpeg_idct(const JpegDesc *__restrict__ descs,
                                                    const int64_t *__restrict__ blk0, int nimg,
-                                                   const uint16_t *__restrict__ qts, uint8_t *__restrict__ work) {
+                                                   const uint16_t *__restrict__ qts, uint8_t *__restrict__ work,
+                                                   int32_t *__restrict__ handover) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < blk0[3 * nimg]; i += (int64_t)gridDim.x * 256)
-    jpeg_idct_block(descs, blk0, nimg, qts, work, i);
+    jpeg_idct_block(descs, blk0, nimg, qts, work, handover, i);
 }
 __device__ __forceinline__ void jpeg_idct_block(const JpegDesc *__restrict__ descs, const int64_t *__restrict__ blk0,
                                                 int nimg, const uint16_t *__restrict__ qts, uint8_t *__restrict__ work,
-                                                int64_t i) {
+                                                int32_t *__restrict__ handover, int64_t i) {
   int lo = 0, hi = 3 * nimg;
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
@@ -446,6 +490,20 @@ __device__ __forceinline__ void jpeg_idct_block(const JpegDesc *__restrict__ des
                               58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 #pragma unroll
   for (int z = 0; z < 64; z++) cf[zz[z]] = (int)in[z] * (int)q[zz[z]];
+  // The decoder the output is compared with runs this transform in SIMD: 16-bit
+  // products and sums, a first pass saturated to 16 bits, samples saturated
+  // instead of looked up in the range-limit table.  It equals jidctint.c (this
+  // code) while every dequantised coefficient and first-pass value is within
+  // +-16383 (no 16-bit sum of two wraps, no 32-bit sum here overflows) and every
+  // sample, before the level shift, within the table's [-512, 511].  Corrupt
+  // data leaves that range: such an image is handed to the host decoder
+  // (handover[image] = 1, FI_EUNSUPPORTED).
+  int dlo = 0, dhi = 0, slo = 0, shi = 0;
+#pragma unroll
+  for (int k = 0; k < 64; k += 2) {
+    dlo = min(dlo, min(cf[k], cf[k + 1]));
+    dhi = max(dhi, max(cf[k], cf[k + 1]));
+  }
   // pass 1: columns
 #pragma unroll
   for (int x = 0; x < 8; x++) {
@@ -491,9 +549,19 @@ __device__ __forceinline__ void jpeg_idct_block(const JpegDesc *__restrict__ des
     ws[24 + x] = (tmp13 + tmp0 + R1) >> S;
     ws[32 + x] = (tmp13 - tmp0 + R1) >> S;
   }
+#pragma unroll
+  for (int k = 0; k < 64; k += 2) {
+    dlo = min(dlo, min(ws[k], ws[k + 1]));
+    dhi = max(dhi, max(ws[k], ws[k + 1]));
+  }
   // pass 2: rows -> samples
   uint8_t *out = work + D.plane[c] + (int64_t)(by * 8) * (D.bw[c] * 8) + bx * 8;
   const int pitch = D.bw[c] * 8;
+  auto limit = [&slo, &shi](int x) {
+    slo = min(slo, x);
+    shi = max(shi, x);
+    return jpeg_range_limit(x);
+  };
 #pragma unroll
   for (int y = 0; y < 8; y++) {
     const int *w = ws + 8 * y;
@@ -529,16 +597,17 @@ __device__ __forceinline__ void jpeg_idct_block(const JpegDesc *__restrict__ des
     tmp3 += z1 + z4;
     constexpr int S = CB + P1 + 3, R2 = 1 << (S - 1);
     uint32_t lo = 0, hi = 0;
-    lo |= (uint32_t)jpeg_range_limit((tmp10 + tmp3 + R2) >> S);
-    lo |= (uint32_t)jpeg_range_limit((tmp11 + tmp2 + R2) >> S) << 8;
-    lo |= (uint32_t)jpeg_range_limit((tmp12 + tmp1 + R2) >> S) << 16;
-    lo |= (uint32_t)jpeg_range_limit((tmp13 + tmp0 + R2) >> S) << 24;
-    hi |= (uint32_t)jpeg_range_limit((tmp13 - tmp0 + R2) >> S);
-    hi |= (uint32_t)jpeg_range_limit((tmp12 - tmp1 + R2) >> S) << 8;
-    hi |= (uint32_t)jpeg_range_limit((tmp11 - tmp2 + R2) >> S) << 16;
-    hi |= (uint32_t)jpeg_range_limit((tmp10 - tmp3 + R2) >> S) << 24;
+    lo |= (uint32_t)limit((tmp10 + tmp3 + R2) >> S);
+    lo |= (uint32_t)limit((tmp11 + tmp2 + R2) >> S) << 8;
+    lo |= (uint32_t)limit((tmp12 + tmp1 + R2) >> S) << 16;
+    lo |= (uint32_t)limit((tmp13 + tmp0 + R2) >> S) << 24;
+    hi |= (uint32_t)limit((tmp13 - tmp0 + R2) >> S);
+    hi |= (uint32_t)limit((tmp12 - tmp1 + R2) >> S) << 8;
+    hi |= (uint32_t)limit((tmp11 - tmp2 + R2) >> S) << 16;
+    hi |= (uint32_t)limit((tmp10 - tmp3 + R2) >> S) << 24;
     *reinterpret_cast<uint2 *>(out + (int64_t)y * pitch) = uint2{lo, hi};
   }
+  if (dlo < -16383 || dhi > 16383 || slo < -512 || shi > 511) handover[R.img] = 1;
 }
 
 // ---------------------------------------------------------------------------
@@ -548,6 +617,8 @@ __device__ __forceinline__ void jpeg_idct_block(const JpegDesc *__restrict__ des
 __device__ __forceinline__ int jpeg_up(const uint8_t *pl, int pitch, int dw, int dh, int hs, int vs, int x, int y) {
   if (hs == 1 && vs == 1) return pl[(int64_t)y * pitch + x];
   const int cx = x >> 1;
+  // jdsample.c jinit_upsampler: the fancy filters only for downsampled_width > 2, else h2v1 / h2v2_upsample (replication)
+  if (dw <= 2) return pl[(int64_t)(vs == 1 ? y : y >> 1) * pitch + cx];
   const int cl = cx > 0 ? cx - 1 : 0, cr = cx < dw - 1 ? cx + 1 : dw - 1;
   const bool odd = x & 1;
   if (vs == 1) {  // h2v1_fancy_upsample
@@ -885,6 +956,10 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
     if (desc_prog[k])
       for (int c = 0; c < descs[k].ncomp; c++) descs[k].coef[c] += (int64_t)work_total;
   const size_t pcoef0 = work_total;
+  // ... and the per-image handover flags (k_jpeg_prog, k_jpeg_idct: corrupt data the host decodes), zeroed with them
+  pcoef_total = (pcoef_total + 255) & ~(size_t)255;
+  const size_t o_hand = pcoef0 + pcoef_total, hand_bytes = descs.size() * sizeof(int32_t);
+  pcoef_total += (hand_bytes + 255) & ~(size_t)255;
   work_total += pcoef_total;
   // scans of one level are independent: one launch per level, in order
   std::stable_sort(pitems.begin(), pitems.end(),
@@ -902,7 +977,7 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   const size_t o_vt = o_view + ((vds.size() * sizeof(JpegViewDesc) + 255) & ~(size_t)255);
   const size_t tab0 = (ecs_total + 255) & ~(size_t)255, up_total = tab0 + o_vt + vt0.size() * 8;
   uint8_t *din = (uint8_t *)alloc(actx, 0, up_total);
-  uint8_t *hst = (uint8_t *)alloc(actx, 3, up_total);
+  uint8_t *hst = (uint8_t *)alloc(actx, 3, up_total + hand_bytes);  // (+ the handover flags, read back)
   uint8_t *dwork = (uint8_t *)alloc(actx, 2, std::max(work_total, (size_t)256));
   if (!din || !hst || !dwork) {
     *err = "memory for the JPEG batch";
@@ -943,24 +1018,25 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
   else
     hipLaunchKernelGGL(k_jpeg_huff<false>, g, dim3(64), 0, st, dd, (const JpegInterval *)(dtab + o_iv),
                        (int)ivs.size(), (const JpegHuff *)(dtab + o_huff), nhuff, dwork);
+  if (hipMemsetAsync(dwork + pcoef0, 0, pcoef_total, st) != hipSuccess) {
+    *err = "JPEG coefficient clear";
+    return FI_EDEVICE;
+  }
   if (!pitems.empty()) {
-    if (hipMemsetAsync(dwork + pcoef0, 0, pcoef_total, st) != hipSuccess) {
-      *err = "JPEG coefficient clear";
-      return FI_EDEVICE;
-    }
     if (stage) stage(actx, "k_jpeg_prog");
     for (size_t a = 0; a < pitems.size();) {
       size_t z = a;
       while (z < pitems.size() && pitems[z].level == pitems[a].level) z++;
       hipLaunchKernelGGL(k_jpeg_prog, dim3((unsigned)(z - a)), dim3(64), 0, st, dd,
                          (const JpegProgItem *)(dtab + o_pit) + a, (int)(z - a), (const JpegHuff *)(dtab + o_huff),
-                         dwork);
+                         dwork, (int32_t *)(dwork + o_hand));
       a = z;
     }
     if (stage) stage(actx, nullptr);
   }
   hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)std::min<int64_t>((nblocks + 255) / 256, 1 << 20)), dim3(256), 0, st, dd,
-                     (const int64_t *)(dtab + o_ref), (int)descs.size(), (const uint16_t *)(dtab + o_qt), dwork);
+                     (const int64_t *)(dtab + o_ref), (int)descs.size(), (const uint16_t *)(dtab + o_qt), dwork,
+                     (int32_t *)(dwork + o_hand));
   if (px0.back() > 0) {
     if (stage) stage(actx, "k_jpeg_color");
     hipLaunchKernelGGL(k_jpeg_color, dim3((unsigned)std::min<int64_t>((px0.back() + 255) / 256, 1 << 20)), dim3(256), 0, st, dd,
@@ -973,10 +1049,16 @@ int jpeg_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *
                        (const JpegViewDesc *)(dtab + o_view), (const int64_t *)(dtab + o_vt), (int)vds.size(), dwork);
     if (stage) stage(actx, nullptr);
   }
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+  // the handover flags come back behind the kernels, into the staging buffer's tail
+  const int32_t *hand = reinterpret_cast<const int32_t *>(hst + up_total);
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpyAsync(hst + up_total, dwork + o_hand, hand_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
     *err = "JPEG decode kernels";
     return FI_EDEVICE;
   }
+  for (size_t k = 0; k < descs.size(); k++)
+    if (hand[k]) status[desc_img[k]] = FI_EUNSUPPORTED;
   return 0;
 }
 

@@ -40,6 +40,26 @@ static size_t scan_end(const uint8_t *d, size_t n, size_t q) {
   return n;
 }
 
+// The restart markers of a scan of nmcu MCUs, segment e[0, len): libjpeg reads
+// one after every `restart` MCUs and expects them numbered 0, 1, ... mod 8
+// (jdmarker.c read_restart_marker); for a skipped, repeated or missing one
+// jpeg_resync_to_restart drops or invents intervals.  Only the regular
+// sequence is decoded here (the intervals are located by their markers); the
+// markers after the last MCU are never read.
+static bool restarts_regular(const uint8_t *e, size_t len, int restart, int nmcu) {
+  if (restart <= 0) return true;
+  const int need = (nmcu + restart - 1) / restart - 1;
+  int seen = 0;
+  for (size_t q = 0; q + 1 < len && seen < need; q++) {
+    if (e[q] == 0xFF && e[q + 1] >= 0xD0 && e[q + 1] <= 0xD7) {
+      if (e[q + 1] - 0xD0 != (seen & 7)) return false;
+      seen++;
+      q++;
+    }
+  }
+  return seen == need;
+}
+
 // One SOS of a progressive stream (s .. e = the marker's payload of length L - 2):
 // jdmarker.c get_sos and jdphuff.c start_pass_phuff_decoder
 static int prog_sos(const uint8_t *d, size_t n, const uint8_t *s, size_t L, const uint8_t *e, bool jfif, bool adobe,
@@ -138,10 +158,17 @@ static int prog_sos(const uint8_t *d, size_t n, const uint8_t *s, size_t L, cons
 
 // at EOI: every coefficient of every component sent and refined to Al = 0
 // (libjpeg smooths the blocks of an incomplete file: jdcoefct.c)
-static int prog_finish(JpegHdr *o, const ProgParse &pp) {
+static int prog_finish(const uint8_t *d, JpegHdr *o, const ProgParse &pp) {
   for (int c = 0; c < o->ncomp; c++)
     for (int z = 0; z < 64; z++)
       if (pp.coef_bits[c][z] != 0) return FI_EUNSUPPORTED;
+  JpegGeom G;
+  jpeg_geom(*o, &G);
+  for (const JpegScan &S : o->scans) {  // (the MCU counts of jpeg_prog_items)
+    const int c = S.ci[0];
+    const int nmcu = S.ns == 1 ? ((G.dw[c] + 7) / 8) * ((G.dh[c] + 7) / 8) : G.mcux * G.mcuy;
+    if (!restarts_regular(d + S.ecs0, S.ecs1 - S.ecs0, S.restart, nmcu)) return FI_EUNSUPPORTED;
+  }
   o->nlevels = 0;
   for (const JpegScan &S : o->scans) o->nlevels = S.level + 1 > o->nlevels ? S.level + 1 : o->nlevels;
   o->ecs1 = o->scans.back().ecs1;
@@ -312,6 +339,9 @@ int jpeg_parse(const uint8_t *d, size_t n, JpegHdr *o, uint32_t flags) {
           const int hv = o->h[0] * 10 + o->v[0];
           if (hv != 11 && hv != 21 && hv != 22) return FI_EUNSUPPORTED;
         }
+        JpegGeom G;
+        jpeg_geom(*o, &G);
+        if (!restarts_regular(d + o->ecs0, o->ecs1 - o->ecs0, o->restart, G.mcux * G.mcuy)) return FI_EUNSUPPORTED;
         return 0;
       }
       case 0xE0:  // APP0 "JFIF\0" (examine_app0: at least 14 data bytes)
@@ -331,7 +361,7 @@ int jpeg_parse(const uint8_t *d, size_t n, JpegHdr *o, uint32_t flags) {
   if (o->progressive && !o->scans.empty()) {
     // the last scan must end at EOI, the last two bytes of the data
     if (p + 2 != n || d[p] != 0xFF || d[p + 1] != 0xD9) return FI_EUNSUPPORTED;
-    return prog_finish(o, pp);
+    return prog_finish(d, o, pp);
   }
   return FI_EINVAL;
 }

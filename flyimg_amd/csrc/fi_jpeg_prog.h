@@ -50,14 +50,18 @@ __host__ __device__ inline bool jpeg_prog_dc_refine(BR &br) {
   return jpeg_prog_bits(br, 1) != 0;
 }
 
-// AC, first pass of the band Ss .. Se
+// AC, first pass of the band Ss .. Se.  Both AC procedures return false where
+// corrupt data makes libjpeg store a coefficient outside the band (it may be
+// in another scan's band, or below 63's guard entry): such an image is left
+// to the host decoder (FI_EUNSUPPORTED; k_jpeg_prog raises a per-image flag).
 template <class OPS, class BR, class TAB>
-__host__ __device__ inline void jpeg_prog_ac_first(BR &br, const TAB *tab, int16_t *b, uint32_t &eobrun, int Ss, int Se,
+__host__ __device__ inline bool jpeg_prog_ac_first(BR &br, const TAB *tab, int16_t *b, uint32_t &eobrun, int Ss, int Se,
                                                    int Al) {
   if (eobrun > 0) {  // the block is part of an end-of-band run
     eobrun--;
-    return;
+    return true;
   }
+  bool ok = true;
   for (int k = Ss; k <= Se; k++) {
     const int rs = OPS::sym(br, tab);
     int r = rs >> 4, s = rs & 15;
@@ -65,7 +69,10 @@ __host__ __device__ inline void jpeg_prog_ac_first(BR &br, const TAB *tab, int16
       k += r;
       const uint32_t v = jpeg_prog_bits(br, s);
       s = v < (1u << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v;
-      if (k <= Se) b[k] = (int16_t)((uint32_t)s << Al);  // (corrupt data: libjpeg writes past the band)
+      if (k <= Se)
+        b[k] = (int16_t)((uint32_t)s << Al);
+      else
+        ok = false;  // (corrupt data: libjpeg writes past the band)
     } else if (r == 15) {
       k += 15;  // ZRL
     } else {    // EOBr: this block and 2^r - 1 + extra bits more
@@ -75,6 +82,7 @@ __host__ __device__ inline void jpeg_prog_ac_first(BR &br, const TAB *tab, int16
       break;
     }
   }
+  return ok;
 }
 
 // AC refinement works on bit masks of the block, bit z = zigzag coefficient z:
@@ -115,10 +123,11 @@ __host__ __device__ inline void jpeg_prog_correct(BR &br, JpegProgRefine &R, uin
 // bit.  Where the run ends depends on the zero positions only, so here it is
 // found from the mask and the correction bits it passes are read in one go.
 template <class OPS, class BR, class TAB>
-__host__ __device__ inline void jpeg_prog_ac_refine(BR &br, const TAB *tab, JpegProgRefine &R, uint32_t &eobrun, int Ss,
+__host__ __device__ inline bool jpeg_prog_ac_refine(BR &br, const TAB *tab, JpegProgRefine &R, uint32_t &eobrun, int Ss,
                                                     int Se) {
   const uint64_t band = jpeg_prog_below(Se + 1);
   int k = Ss;
+  bool ok = true;
   if (eobrun == 0) {
     for (; k <= Se; k++) {
       const int rs = OPS::sym(br, tab);
@@ -138,13 +147,17 @@ __host__ __device__ inline void jpeg_prog_ac_refine(BR &br, const TAB *tab, Jpeg
       const int kend = zm ? __builtin_ctzll(zm) : Se + 1;  // the target zero coefficient
       jpeg_prog_correct<OPS>(br, R, R.nz & from & jpeg_prog_below(kend));
       k = kend;
-      if (s && k <= Se) (s > 0 ? R.newp : R.newm) |= (uint64_t)1 << k;  // (corrupt data: libjpeg stores at k = Se + 1 too)
+      if (s && k <= Se)
+        (s > 0 ? R.newp : R.newm) |= (uint64_t)1 << k;
+      else if (s)
+        ok = false;  // (corrupt data: libjpeg stores at k = Se + 1 too)
     }
   }
   if (eobrun > 0) {  // correction bits for the rest of the band
     if (k <= Se) jpeg_prog_correct<OPS>(br, R, R.nz & band & ~jpeg_prog_below(k));
     eobrun--;
   }
+  return ok;
 }
 
 // coefficient z after the refinement: jdphuff.c's p1 / m1 rule

@@ -16,19 +16,22 @@ namespace fi {
 namespace {
 
 // jdhuff.c jpeg_fill_bit_buffer over [pos, end): stuffed 0xFF00 -> 0xFF; a
-// marker or the end of the scan feeds zero bits
+// marker or the end of the scan feeds zero bits, counted in `fake` as
+// fi_jpeg.hip's BitReader counts them
 struct HostBitReader {
   const uint8_t *p;
   int pos, end;
   uint64_t buf;
-  int nbits;
+  int nbits, fake;
   bool marker;
+  bool short_of_data() const { return nbits < fake; }
   void init(const uint8_t *seg, int byte0, int end_) {
     p = seg;
     pos = byte0;
     end = end_;
     buf = 0;
     nbits = 0;
+    fake = 0;
     marker = false;
   }
   void fill() {
@@ -42,10 +45,13 @@ struct HostBitReader {
           } else {
             marker = true;
             b = 0;
+            fake += 8;
           }
         } else {
           pos++;
         }
+      } else {
+        fake += 8;
       }
       buf = (buf << 8) | b;
       nbits += 8;
@@ -69,7 +75,10 @@ struct HostOps {  // jpeg_decode_sym of fi_jpeg.hip
       l++;
       code = (int32_t)br.peek(l);
     }
-    if (l > 16) return 0;  // corrupt data: jdhuff.c warns and returns 0
+    if (l > 16) {  // corrupt data: jdhuff.c warns and returns 0, the 17 bits it tried consumed
+      br.skip(17);
+      return 0;
+    }
     br.skip(l);
     return t->huffval[(code + t->valoff[l]) & 255];
   }
@@ -114,7 +123,8 @@ int jpeg_prog_coefs_host(const uint8_t *data, size_t len, uint32_t flags, JpegHd
     const JpegHuff *tab[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < 3; k++)
       if (I.tab[k] >= 0) tab[k] = &huffs[I.tab[k]];
-    for (int mcu = I.mcu0; mcu < I.mcu1; mcu++) {
+    // (jdphuff.c insufficient_data: the MCU it was raised in is finished, the later ones are left alone)
+    for (int mcu = I.mcu0; mcu < I.mcu1 && !br.short_of_data(); mcu++) {
       if (I.Ss != 0 && I.Ah == 0 && S.eobrun > 0) {  // a first-pass run leaves its blocks zero
         const uint32_t skip = std::min<uint32_t>(S.eobrun, (uint32_t)(I.mcu1 - mcu));
         S.eobrun -= skip;
@@ -133,14 +143,14 @@ int jpeg_prog_coefs_host(const uint8_t *data, size_t len, uint32_t flags, JpegHd
               else if (jpeg_prog_dc_refine(br))
                 b[0] = (int16_t)(b[0] | (1 << I.Al));
             } else if (I.Ah == 0) {
-              jpeg_prog_ac_first<HostOps>(br, tab[0], b, S.eobrun, I.Ss, I.Se, I.Al);
+              if (!jpeg_prog_ac_first<HostOps>(br, tab[0], b, S.eobrun, I.Ss, I.Se, I.Al)) return FI_EUNSUPPORTED;
             } else {
               JpegProgRefine R{};
               for (int z = I.Ss; z <= I.Se; z++) {
                 R.nz |= (uint64_t)(b[z] != 0) << z;
                 R.has |= (uint64_t)((b[z] & (1 << I.Al)) != 0) << z;
               }
-              jpeg_prog_ac_refine<HostOps>(br, tab[0], R, S.eobrun, I.Ss, I.Se);
+              if (!jpeg_prog_ac_refine<HostOps>(br, tab[0], R, S.eobrun, I.Ss, I.Se)) return FI_EUNSUPPORTED;
               for (int z = I.Ss; z <= I.Se; z++) b[z] = jpeg_prog_refined(b[z], z, R, I.Al);
             }
           }

@@ -308,7 +308,12 @@ int fi_debug_monochrome(fi_ctx *ctx, const uint16_t *gray, int32_t w, int32_t h,
  * fi_jpeg_decode_device: decodes n streams (host memory) into caller device
  * buffers dst[i] (HWC rows of dst_stride[i] bytes; out_channels 0 = the
  * source's, 3 = RGB for every source, gray replicated) and waits; status[i]
- * per image; returns the first failing status (the others are decoded). */
+ * per image; returns the first failing status (the others are decoded).
+ * Damaged streams decode as libjpeg decodes them (entropy data that runs out
+ * leaves the rest of its restart interval grey) or are FI_EUNSUPPORTED:
+ * restart markers out of sequence already in fi_jpeg_info; corrupt data whose
+ * coefficients leave the range in which the decoders agree only in the
+ * decode's status[i], so a caller always handles FI_EUNSUPPORTED there. */
 int fi_jpeg_info(const uint8_t *data, size_t len, int32_t *w, int32_t *h, int32_t *channels);
 int fi_jpeg_decode_device(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
                           uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,

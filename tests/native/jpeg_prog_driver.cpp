@@ -2,7 +2,8 @@
 // (fi_jpeg_parse.cpp), the scan scheduler (jpeg_prog_items) and the host
 // entropy decoder (fi_jpeg_prog_host.cpp), which runs the block procedures of
 // fi_jpeg_prog.h that k_jpeg_prog runs on the device.  Every file named on
-// the command line must decode; then every 7th truncation and 3000 seeded
+// the command line must decode (the damaged streams after "--damaged" may also
+// be handed to the host, FI_EUNSUPPORTED); then every 7th truncation and 3000 seeded
 // mutations of it (half of them in the entropy-coded bytes) are run.  The
 // input, segment and coefficient buffers are exact-size heap allocations, so
 // any access outside them trips ASan.  The mutants of a file are spread over
@@ -27,14 +28,20 @@ static int run(const std::vector<uint8_t> &t) {
 int main(int argc, char **argv) {
   long n = 0;
   std::atomic<long> decoded(0);
+  bool damaged = false;
   for (int a = 1; a < argc; a++) {
+    if (std::string(argv[a]) == "--damaged") {
+      damaged = true;
+      continue;
+    }
     FILE *f = fopen(argv[a], "rb");
     if (!f) return 2;
     std::vector<uint8_t> d;
     int ch;
     while ((ch = fgetc(f)) != EOF) d.push_back((uint8_t)ch);
     fclose(f);
-    if (run(d) != 0) {
+    const int rc = run(d);
+    if (rc != 0 && !(damaged && rc == FI_EUNSUPPORTED)) {
       fprintf(stderr, "%s does not decode\n", argv[a]);
       return 3;
     }

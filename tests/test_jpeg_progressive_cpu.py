@@ -21,6 +21,9 @@ from PIL import Image
 from flyimg_amd import _lib as L
 from flyimg_amd.runtime import jpeg_coefs_host, jpeg_info, jpeg_scan_info, jpeg_scan_status
 
+from tests import _jpeg_files
+from tests._jpeg_files import ZZ, _idct_plane, _islow_1d  # noqa: F401  (the integer-exact plane reference)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -146,46 +149,6 @@ def test_rejections_under_the_flag():
 
 
 # ---- the host entropy core, exact -------------------------------------------
-ZZ = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,
-               7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31,
-               39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
-
-
-def _islow_1d(v, shift):
-    """jidctint.c jpeg_idct_islow, one pass over the last axis of int32 v (.., 8)."""
-    F0298, F0390, F0541, F0765, F0899, F1175 = 2446, 3196, 4433, 6270, 7373, 9633
-    F1501, F1847, F1961, F2053, F2562, F3072 = 12299, 15137, 16069, 16819, 20995, 25172
-    z2, z3 = v[..., 2], v[..., 6]
-    z1 = (z2 + z3) * F0541
-    tmp2 = z1 + z3 * (-F1847)
-    tmp3 = z1 + z2 * F0765
-    tmp0 = (v[..., 0] + v[..., 4]) << 13
-    tmp1 = (v[..., 0] - v[..., 4]) << 13
-    tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
-    tmp0, tmp1, tmp2, tmp3 = v[..., 7], v[..., 5], v[..., 3], v[..., 1]
-    z1, z2, z3, z4 = tmp0 + tmp3, tmp1 + tmp2, tmp0 + tmp2, tmp1 + tmp3
-    z5 = (z3 + z4) * F1175
-    tmp0, tmp1, tmp2, tmp3 = tmp0 * F0298, tmp1 * F2053, tmp2 * F3072, tmp3 * F1501
-    z1, z2, z3, z4 = z1 * -F0899, z2 * -F2562, z3 * -F1961 + z5, z4 * -F0390 + z5
-    tmp0, tmp1, tmp2, tmp3 = tmp0 + z1 + z3, tmp1 + z2 + z4, tmp2 + z2 + z3, tmp3 + z1 + z4
-    r = 1 << (shift - 1)
-    return np.stack([tmp10 + tmp3, tmp11 + tmp2, tmp12 + tmp1, tmp13 + tmp0,
-                     tmp13 - tmp0, tmp12 - tmp1, tmp11 - tmp2, tmp10 - tmp3], -1) + r >> shift
-
-
-def _idct_plane(blocks, qt):
-    """(bh, bw, 64) zigzag int16 blocks + natural-order quant table -> u8 plane (bh * 8, bw * 8)."""
-    bh, bw, _ = blocks.shape
-    nat = np.zeros((bh, bw, 64), np.int32)
-    nat[..., ZZ] = blocks.astype(np.int32)
-    cf = (nat * qt.astype(np.int32)).reshape(bh, bw, 8, 8)
-    ws = _islow_1d(cf.swapaxes(-1, -2), 13 - 2).swapaxes(-1, -2)  # pass 1: columns
-    out = _islow_1d(ws, 13 + 2 + 3)                               # pass 2: rows
-    m = out & 1023                                                # range_limit[x & RANGE_MASK]
-    px = np.clip(np.where(m >= 512, m - 1024, m) + 128, 0, 255).astype(np.uint8)
-    return px.transpose(0, 2, 1, 3).reshape(bh * 8, bw * 8)
-
-
 GRAY_CASES = [(1, 1, 30), (1, 1, 90), (33, 17, 30), (33, 17, 90), (97, 61, 30), (97, 61, 90)]
 
 
@@ -252,6 +215,14 @@ def test_progressive_host_path_under_asan_ubsan():
             files.append(os.path.join(d, name))
             with open(files[-1], "wb") as f:
                 f.write(blob)
+        # ... and damaged progressive streams of tests/_jpeg_files.py: scans and intervals cut short, restart
+        # markers lost or renumbered (decoded, or handed to the host by the parser or the entropy core)
+        files.append("--damaged")
+        for dm in _jpeg_files.corpus_b():
+            if dm.progressive and ("pgrey_scan" in dm.name or "pgrey_dri_scan_3" in dm.name or "p420_scan_5" in dm.name):
+                files.append(os.path.join(d, dm.name + ".jpg"))
+                with open(files[-1], "wb") as f:
+                    f.write(dm.blob)
         r = subprocess.run([exe, *files], capture_output=True, text=True, timeout=600, env=ENV)
         assert r.returncode == 0, r.stderr[-4000:]
         assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
