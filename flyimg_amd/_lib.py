@@ -22,6 +22,7 @@ FI_EDEVICE = -4
 FI_EUNSUPPORTED = -5
 FI_ECAPACITY = -6
 FI_JPEG_PROGRESSIVE = 1  # fi_jpeg_info_ex / fi_jpeg_decode_device_ex flags
+FI_JPEG_ENC_PROGRESSIVE = 1  # fi_jpeg_encode_bound_ex / fi_jpeg_encode_device_ex flags
 FI_PNG_META_ORIENT = 1  # fi_png_info meta: a chunk Pillow's exif_transpose could take an orientation from
 
 FI_OP_THUMBNAIL = 1 << 0
@@ -209,6 +210,10 @@ def lib():
                                            ctypes.c_size_t]
     L.fi_jpeg_encode_bound.argtypes = [i32, i32, i32, i32, i32, P(ctypes.c_size_t)]
     L.fi_jpeg_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.fi_jpeg_encode_bound_ex.argtypes = [i32, i32, i32, i32, i32, ctypes.c_uint32, P(ctypes.c_size_t)]
+    L.fi_jpeg_encode_device_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, ctypes.c_uint32]
+    L.fi_debug_jpeg_prog_write_host.argtypes = [vp, ctypes.c_size_t, i32, i32, i32, i32, i32, vp, ctypes.c_size_t,
+                                                P(ctypes.c_size_t), P(i32)]
     L.fi_png_encode_bound.argtypes = [i32, i32, i32, P(ctypes.c_size_t)]
     L.fi_png_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.fi_png_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(i32), P(i32), P(i32), P(i32), P(i32)]

@@ -169,7 +169,11 @@ class CodecPipeline:
     call; outputs with alpha still go through the host PNG writer unless
     ``gpu_png`` (off by default, needs ``gpu_encode``) sends them through one
     fi_png_encode_device call per batch: other bytes than the host writer's
-    file, the same decoded pixels.  With
+    file, the same decoded pixels.  With ``gpu_progressive_encode`` (off by
+    default, needs ``gpu_encode``) the JPEGs are the file class flyimg ships:
+    progressive, with Huffman tables fitted to every scan
+    (FI_JPEG_ENC_PROGRESSIVE) -- smaller files, the same decoded pixels,
+    more device time; DESIGN.md 3.6b.  With
     ``gpu_progressive`` (off by default) progressive JPEG sources join the GPU
     decode batch instead of the host threads (same pixels).  A progressive
     scan is one serial chain on the GPU: measured on 1080p sources the GPU
@@ -193,7 +197,9 @@ class CodecPipeline:
 
     def __init__(self, ctx, threads: int = 16, gpu_decode: bool = True, gpu_encode: bool = False,
                  gpu_progressive: bool = False, gpu_orient: bool = False, gpu_png: bool = False,
-                 gpu_png_decode: bool = False):
+                 gpu_png_decode: bool = False, gpu_progressive_encode: bool = False):
+        if gpu_progressive_encode and not gpu_encode:
+            raise ValueError("gpu_progressive_encode needs gpu_encode=True: it selects the GPU encoder's file class")
         if gpu_png and not gpu_encode:
             raise ValueError("gpu_png needs gpu_encode=True: the PNG outputs are written by the GPU encode stage")
         self.ctx = ctx
@@ -204,6 +210,7 @@ class CodecPipeline:
         self.gpu_orient = gpu_orient
         self.gpu_png = gpu_png
         self.gpu_png_decode = gpu_png_decode
+        self.gpu_progressive_encode = gpu_progressive_encode
         self.decode_stats = {"gpu": 0, "host": 0}  # images ``process`` decoded on the GPU / on the host
         # ``process``: host seconds in the encode stage, the bytes its outputs
         # were as pixels and are as files (with gpu_encode, what crosses PCIe)
@@ -329,7 +336,8 @@ class CodecPipeline:
                     L.FI_EINVAL, msg.decode() if msg else f"image {i}: PNG encode"))
             encoded[i] = f
         qs = [int(quality[i]) for i in idx]
-        files = self.ctx.jpeg_encode(views, qs, [0 if q >= 90 else 2 for q in qs])
+        files = self.ctx.jpeg_encode(views, qs, [0 if q >= 90 else 2 for q in qs],
+                                     progressive=self.gpu_progressive_encode)
         for i, f in zip(idx, files):
             if f is None:
                 msg = L.lib().fi_last_error()

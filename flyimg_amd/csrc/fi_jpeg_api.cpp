@@ -121,11 +121,43 @@ static void jpeg_enc_stage(void *actx, const char *name) {  // ends the running 
   delete c->jpeg_enc_timer;
   c->jpeg_enc_timer = name ? new Timer(c, name, 0) : nullptr;
 }
+int fi_jpeg_encode_bound_ex(int32_t w, int32_t h, int32_t channels, int32_t quality, int32_t subsampling,
+                            uint32_t flags, size_t *bytes) {
+  if (!bytes || (flags & ~FI_JPEG_ENC_PROGRESSIVE)) return set_err(FI_EINVAL, "bad arguments");
+  if (!flags) return fi_jpeg_encode_bound(w, h, channels, quality, subsampling, bytes);
+  const int rc = jpeg_penc_bound(w, h, channels, quality, subsampling, bytes);
+  if (rc)
+    return set_err(rc, rc == FI_EUNSUPPORTED ? "channel count or subsampling the GPU JPEG encoder does not write"
+                                             : "bad JPEG dimensions or quality");
+  return FI_OK;
+}
+// Test hook: the progressive encoder's host model (fi_jpeg_pwrite.cpp)
+int fi_debug_jpeg_prog_write_host(const int16_t *coefs, size_t ncoefs, int32_t w, int32_t h, int32_t channels,
+                                  int32_t quality, int32_t subsampling, uint8_t *out, size_t out_cap,
+                                  size_t *out_len, int32_t *flushes) {
+  if (!coefs || !out_len || !flushes || (out_cap && !out)) return set_err(FI_EINVAL, "bad arguments");
+  std::vector<uint8_t> file;
+  int fl = 0;
+  const int rc = jpeg_penc_write(coefs, ncoefs, w, h, channels, quality, subsampling, &file, &fl);
+  if (rc) return set_err(rc, "settings the progressive writer turns down, or a coefficient count that does not fit them");
+  *out_len = file.size();
+  *flushes = fl;
+  if (file.size() > out_cap) return set_err(FI_ENOMEM, "out_cap is below the file size (out_len)");
+  memcpy(out, file.data(), file.size());
+  return FI_OK;
+}
 int fi_jpeg_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w, const int32_t *h,
                           const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
                           const int32_t *subsampling, int32_t n, uint8_t *const *out, const size_t *out_cap,
                           size_t *out_len, int32_t *status) {
-  if (!c || n < 0 ||
+  return fi_jpeg_encode_device_ex(c, src, w, h, channels, src_stride, quality, subsampling, n, out, out_cap, out_len,
+                                  status, 0);
+}
+int fi_jpeg_encode_device_ex(fi_ctx *c, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                             const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
+                             const int32_t *subsampling, int32_t n, uint8_t *const *out, const size_t *out_cap,
+                             size_t *out_len, int32_t *status, uint32_t flags) {
+  if (!c || n < 0 || (flags & ~FI_JPEG_ENC_PROGRESSIVE) ||
       (n > 0 && (!src || !w || !h || !channels || !src_stride || !quality || !subsampling || !out || !out_cap ||
                  !out_len || !status)))
     return set_err(FI_EINVAL, "bad arguments");
@@ -134,8 +166,9 @@ int fi_jpeg_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w
   std::lock_guard<std::mutex> lk(c->mu);
   if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
   std::string err;
-  const int rc = jpeg_encode_batch(c->stream, src, w, h, channels, src_stride, quality, subsampling, n, out, out_cap,
-                                   out_len, status, jpeg_enc_alloc, jpeg_enc_stage, c, &err);
+  const int rc = (flags & FI_JPEG_ENC_PROGRESSIVE ? jpeg_pencode_batch : jpeg_encode_batch)(
+      c->stream, src, w, h, channels, src_stride, quality, subsampling, n, out, out_cap, out_len, status,
+      jpeg_enc_alloc, jpeg_enc_stage, c, &err);
   jpeg_enc_stage(c, nullptr);
   collect_timers(c);
   if (rc) return set_err(rc, "%s", err.c_str());

@@ -33,4 +33,23 @@ size_t jpeg_enc_slot_bytes(int bpm, int mcux);
 // upper bound of the whole file; 0 = OK
 int jpeg_enc_bound(int w, int h, int channels, int quality, int subsampling, size_t *bytes);
 
+// Progressive files with per-scan optimal tables (fi_jpeg_pwrite.cpp; the
+// entropy coder itself is fi_jpeg_pcore.h, shared with the kernels), as
+// libjpeg-turbo writes them for progressive=True, restart_marker_rows=1.
+// SOI, APP0, DQT, SOF2: everything before the first scan's tables
+void jpeg_penc_write_head(int w, int h, int channels, int quality, int subsampling, std::vector<uint8_t> *out);
+// what follows scan s's DHT segments: DRI where the scan's interval differs
+// from *last_interval (updated), then SOS
+void jpeg_penc_write_scan_tail(int w, int h, int channels, int subsampling, int s, int *last_interval,
+                               std::vector<uint8_t> *out);
+// upper bound of the whole progressive file; 0 = OK (the statuses of jpeg_enc_check)
+int jpeg_penc_bound(int w, int h, int channels, int quality, int subsampling, size_t *bytes);
+// The host model: the file of the quantised coefficients `coefs` (zigzag int16
+// blocks, a plane per component padded to whole MCUs: what
+// fi_debug_jpeg_coefs_host hands out; ncoefs of them).  *flushes = the
+// correction-buffer flushes inside EOB runs.  0, a status of jpeg_enc_check,
+// or FI_EINVAL for a coefficient count that does not fit the geometry.
+int jpeg_penc_write(const int16_t *coefs, size_t ncoefs, int w, int h, int channels, int quality, int subsampling,
+                    std::vector<uint8_t> *out, int *flushes);
+
 }  // namespace fi

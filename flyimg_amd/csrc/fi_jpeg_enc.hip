@@ -33,22 +33,10 @@
 
 #include "fi_internal.h"
 #include "fi_jpeg_enc.h"
+#include "fi_jpeg_enc_dev.h"
 
 namespace fi {
 
-struct JpegEncDesc {     // one image of an encode batch
-  const uint8_t *src;    // HWC u8, 1 or 3 channels
-  int64_t stride;
-  int32_t W, H, C;
-  int32_t bpm;           // blocks per MCU: 1 gray, 3 4:4:4, 6 4:2:0 (Y Y Y Y Cb Cr)
-  int32_t mcux, mcuy;
-  int32_t qt;            // index of its table pair (u16 [2][64], natural order)
-  int32_t iv0;           // its first restart interval in the batch
-  int64_t blk0;          // its first block in the batch (blocks in MCU order)
-  int64_t slot0;         // byte offset of its first interval slot
-  int64_t slot_bytes;    // bytes per slot
-  int32_t hdr_off, hdr_len;  // its header bytes in the upload
-};
 struct JpegEncIv {       // one restart interval = one MCU row
   int32_t img, row;
 };
@@ -312,6 +300,12 @@ __global__ __launch_bounds__(256) void k_jpeg_fdct(const JpegEncDesc *__restrict
     for (int t = 0; t < 8; t++) dst[t] = reinterpret_cast<const uint4 *>(o)[t];
     acbits[i] = (uint16_t)bits;
   }
+}
+
+void jpeg_enc_launch_fdct(hipStream_t st, const JpegEncDesc *descs, int nimg, int64_t nblocks, const uint16_t *qts,
+                          const uint32_t *huff, int16_t *coef, uint16_t *acbits) {
+  hipLaunchKernelGGL(k_jpeg_fdct, dim3((unsigned)std::min<int64_t>((nblocks + 255) / 256, 1 << 20)), dim3(256), 0, st,
+                     descs, nimg, nblocks, qts, huff, coef, acbits);
 }
 
 __device__ __forceinline__ int jpeg_enc_scan64(int v) {  // inclusive prefix sum over the wave
@@ -598,8 +592,7 @@ int jpeg_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
   int64_t *divdst = (int64_t *)(dwork + k_ivdst);
   int64_t *dpos = (int64_t *)(dwork + k_pos);
   stage(actx, "k_jpeg_fdct");
-  hipLaunchKernelGGL(k_jpeg_fdct, dim3((unsigned)std::min<int64_t>((nblocks + 255) / 256, 1 << 20)), dim3(256), 0, st, dd,
-                     nd, nblocks, (const uint16_t *)(dup + o_qt), dhuff, dcoef, dbits);
+  jpeg_enc_launch_fdct(st, dd, nd, nblocks, (const uint16_t *)(dup + o_qt), dhuff, dcoef, dbits);
   stage(actx, "k_jpeg_henc");
   hipLaunchKernelGGL(k_jpeg_henc, dim3((unsigned)niv), dim3(64), 0, st, dd, div, niv, dhuff, dcoef, dbits,
                      dwork + k_slots, divlen);

@@ -71,6 +71,12 @@ int jpeg_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
                       const int32_t *subsampling, int n, uint8_t *const *out, const size_t *out_cap, size_t *out_len,
                       int32_t *status, void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *),
                       void *actx, std::string *err);
+// the same batch as progressive files with optimal tables (fi_jpeg_penc.hip)
+int jpeg_pencode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                       const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
+                       const int32_t *subsampling, int n, uint8_t *const *out, const size_t *out_cap, size_t *out_len,
+                       int32_t *status, void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *),
+                       void *actx, std::string *err);
 int png_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w, const int32_t *h,
                      const int32_t *channels, const int64_t *src_stride, const int32_t *filter, int n,
                      uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status,

@@ -138,13 +138,33 @@ def jpeg_coefs_host(blob: bytes, progressive: bool = True):
             [qt[64 * k:64 * k + 64] for k in range(n)])
 
 
-def jpeg_encode_bound(w: int, h: int, channels: int, quality: int, subsampling: int = 0) -> int:
+def jpeg_encode_bound(w: int, h: int, channels: int, quality: int, subsampling: int = 0,
+                      progressive: bool = False) -> int:
     """fi_jpeg_encode_bound: an upper bound of the GPU encoder's file size for
     any image of this geometry (host only); raises FiError for arguments the
-    encoder turns down."""
+    encoder turns down.  ``progressive``: the bound of the progressive encoder
+    (fi_jpeg_encode_bound_ex with FI_JPEG_ENC_PROGRESSIVE)."""
     n = ctypes.c_size_t()
-    L.check(L.lib().fi_jpeg_encode_bound(w, h, channels, quality, subsampling, ctypes.byref(n)))
+    if progressive:
+        L.check(L.lib().fi_jpeg_encode_bound_ex(w, h, channels, quality, subsampling, L.FI_JPEG_ENC_PROGRESSIVE,
+                                                ctypes.byref(n)))
+    else:
+        L.check(L.lib().fi_jpeg_encode_bound(w, h, channels, quality, subsampling, ctypes.byref(n)))
     return n.value
+
+
+def jpeg_prog_write_host(coefs, w: int, h: int, channels: int, quality: int, subsampling: int = 0):
+    """fi_debug_jpeg_prog_write_host (test hook): the progressive encoder's host
+    model on quantised coefficients -- the per-component (bh, bw, 64) arrays
+    of ``jpeg_coefs_host`` -- as (file bytes, correction-buffer flushes inside
+    EOB runs)."""
+    co = np.ascontiguousarray(np.concatenate([np.asarray(c, np.int16).ravel() for c in coefs]))
+    cap = jpeg_encode_bound(w, h, channels, quality, subsampling, progressive=True)
+    out = np.empty(cap, np.uint8)
+    n, fl = ctypes.c_size_t(), ctypes.c_int32()
+    L.check(L.lib().fi_debug_jpeg_prog_write_host(co.ctypes.data, co.size, w, h, channels, quality, subsampling,
+                                                  out.ctypes.data, cap, ctypes.byref(n), ctypes.byref(fl)))
+    return out[:n.value].tobytes(), fl.value
 
 
 def png_encode_bound(w: int, h: int, channels: int) -> int:
@@ -462,42 +482,49 @@ class Context:
             for p in ptrs:
                 self.free(p)
 
-    def _jpeg_encode_call(self, views, qs, ss, ptrs, caps):
+    def _jpeg_encode_call(self, views, qs, ss, ptrs, caps, progressive=False):
         n = len(views)
         I32, I64, SZ, VP = ctypes.c_int32 * n, ctypes.c_int64 * n, ctypes.c_size_t * n, ctypes.c_void_p * n
         out_len, status = SZ(), I32()
-        rc = self._lib.fi_jpeg_encode_device(
-            self.h, VP(*[v[0] for v in views]), I32(*[v[1] for v in views]), I32(*[v[2] for v in views]),
-            I32(*[v[4] for v in views]), I64(*[v[3] for v in views]), I32(*qs), I32(*ss), n,
-            VP(*ptrs), SZ(*caps), out_len, status)
+        args = (self.h, VP(*[v[0] for v in views]), I32(*[v[1] for v in views]), I32(*[v[2] for v in views]),
+                I32(*[v[4] for v in views]), I64(*[v[3] for v in views]), I32(*qs), I32(*ss), n,
+                VP(*ptrs), SZ(*caps), out_len, status)
+        if progressive:
+            rc = self._lib.fi_jpeg_encode_device_ex(*args, L.FI_JPEG_ENC_PROGRESSIVE)
+        else:
+            rc = self._lib.fi_jpeg_encode_device(*args)
         return rc, list(status), list(out_len)
 
-    def _jpeg_bound(self, view, q, s):
+    def _jpeg_bound(self, view, q, s, progressive=False):
         b = ctypes.c_size_t()
-        return b.value if self._lib.fi_jpeg_encode_bound(view[1], view[2], view[4], q, s, ctypes.byref(b)) == L.FI_OK else 1
+        rc = self._lib.fi_jpeg_encode_bound_ex(view[1], view[2], view[4], q, s,
+                                               L.FI_JPEG_ENC_PROGRESSIVE if progressive else 0, ctypes.byref(b))
+        return b.value if rc == L.FI_OK else 1
 
-    def jpeg_encode_raw(self, views, quality, subsampling, caps=None):
+    def jpeg_encode_raw(self, views, quality, subsampling, caps=None, progressive=False):
         """fi_jpeg_encode_device on (device pointer, w, h, stride, channels)
         views; ``quality`` / ``subsampling`` per image or one value for all;
         ``caps``: output capacities (default: fi_jpeg_encode_bound, 1 where the
         bound turns the image down).  Returns (rc, status list, length list,
         output buffer list): buffer i is a uint8 array of caps[i] + 64 bytes
         whose last 128 are set to 0xA5 beforehand, so a caller can see what
-        was written behind the file and behind the capacity."""
+        was written behind the file and behind the capacity.
+        ``progressive``: fi_jpeg_encode_device_ex with FI_JPEG_ENC_PROGRESSIVE
+        and its bound."""
         n = len(views)
         qs = list(quality) if isinstance(quality, (list, tuple)) else [quality] * n
         ss = list(subsampling) if isinstance(subsampling, (list, tuple)) else [subsampling] * n
         if caps is None:
-            caps = [self._jpeg_bound(v, q, s) for v, q, s in zip(views, qs, ss)]
+            caps = [self._jpeg_bound(v, q, s, progressive) for v, q, s in zip(views, qs, ss)]
         offs = np.concatenate([[0], np.cumsum([c + 64 for c in caps])]).astype(np.int64)
         pool = np.empty(int(offs[-1]), np.uint8)
         bufs = [pool[int(offs[i]):int(offs[i + 1])] for i in range(n)]
         for b, c in zip(bufs, caps):
             b[max(0, c - 64):] = 0xA5
-        rc, status, lens = self._jpeg_encode_call(views, qs, ss, [b.ctypes.data for b in bufs], caps)
+        rc, status, lens = self._jpeg_encode_call(views, qs, ss, [b.ctypes.data for b in bufs], caps, progressive)
         return rc, status, lens, bufs
 
-    def jpeg_encode(self, views, quality, subsampling) -> list[bytes | None]:
+    def jpeg_encode(self, views, quality, subsampling, progressive=False) -> list[bytes | None]:
         """fi_jpeg_encode_device: baseline JPEG files of device-resident images
         given as (device pointer, w, h, stride, channels) views -- byte for
         byte what Pillow writes with quality / subsampling (0 = 4:4:4, 2 =
@@ -506,19 +533,23 @@ class Context:
         bad quality).  The output buffers are sized to the pixels (the worst
         case of fi_jpeg_encode_bound is many times a real file); the rare file
         larger than its pixels -- noise at the top qualities -- is encoded
-        again into a buffer of the size the first call reported."""
+        again into a buffer of the size the first call reported.
+        ``progressive``: progressive files with per-scan optimal Huffman
+        tables instead (FI_JPEG_ENC_PROGRESSIVE) -- byte for byte what Pillow
+        writes with progressive=True added."""
         n = len(views)
         if not n:
             return []
         qs = list(quality) if isinstance(quality, (list, tuple)) else [quality] * n
         ss = list(subsampling) if isinstance(subsampling, (list, tuple)) else [subsampling] * n
-        caps = [min(self._jpeg_bound(v, q, s), v[1] * v[2] * v[4] + 1024) for v, q, s in zip(views, qs, ss)]
+        caps = [min(self._jpeg_bound(v, q, s, progressive), v[1] * v[2] * v[4] + 1024)
+                for v, q, s in zip(views, qs, ss)]
         offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
         pool = getattr(self, "_enc_out", None)  # the output pool of jpeg_encode and png_encode alike
         if pool is None or pool.size < int(offs[-1]):  # kept: fresh pages are the cost of a large buffer
             pool = self._enc_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
         base = pool.ctypes.data
-        rc, status, lens = self._jpeg_encode_call(views, qs, ss, [base + int(o) for o in offs[:-1]], caps)
+        rc, status, lens = self._jpeg_encode_call(views, qs, ss, [base + int(o) for o in offs[:-1]], caps, progressive)
         if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL) and not (rc == L.FI_ENOMEM and rc in status):
             L.check(rc)  # a failure of the call, not of an image
         files = [pool[int(offs[i]):int(offs[i]) + lens[i]].tobytes() if status[i] == L.FI_OK else None for i in range(n)]
@@ -527,13 +558,13 @@ class Context:
             big = [np.empty(lens[i], np.uint8) for i in again]
             rc, st2, len2 = self._jpeg_encode_call([views[i] for i in again], [qs[i] for i in again],
                                                    [ss[i] for i in again], [b.ctypes.data for b in big],
-                                                   [lens[i] for i in again])
+                                                   [lens[i] for i in again], progressive)
             L.check(rc)
             for k, i in enumerate(again):
                 files[i] = big[k][:len2[k]].tobytes()
         return files
 
-    def jpeg_encode_host(self, images: list[np.ndarray], quality, subsampling) -> list[bytes | None]:
+    def jpeg_encode_host(self, images: list[np.ndarray], quality, subsampling, progressive=False) -> list[bytes | None]:
         """jpeg_encode of host arrays (HW, HWC with 1..4 channels), uploaded to
         scratch device buffers first (tests / tools): the counterpart of
         jpeg_decode_host."""
@@ -545,7 +576,7 @@ class Context:
                 self.h2d(p, a)
                 c = a.shape[2] if a.ndim == 3 else 1
                 views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
-            return self.jpeg_encode(views, quality, subsampling)
+            return self.jpeg_encode(views, quality, subsampling, progressive)
         finally:
             for p in ptrs:
                 self.free(p)

@@ -404,6 +404,33 @@ int fi_jpeg_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t 
                           const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
                           const int32_t *subsampling, int32_t n, uint8_t *const *out, const size_t *out_cap,
                           size_t *out_len, int32_t *status);
+/* Progressive GPU JPEG encode (opt-in): flags = FI_JPEG_ENC_PROGRESSIVE writes
+ * the file class flyimg ships -- SOF2, the scan script of libjpeg's
+ * jpeg_simple_progression (10 scans for YCbCr, 6 for gray), Huffman tables
+ * fitted to every scan, one restart interval per block row of every scan --
+ * byte-identical with libjpeg-turbo's file for the same pixels and settings
+ * (Pillow: Image.save(buf, "JPEG", quality=q, subsampling=s, progressive=True,
+ * restart_marker_rows=1)).  Arguments, statuses and the out_cap rule are those
+ * of fi_jpeg_encode_bound / fi_jpeg_encode_device; with flags 0 both calls are
+ * those functions; any other flag bit is FI_EINVAL.  Kernel times:
+ * "k_jpeg_fdct", "k_jpeg_pstat", "k_jpeg_ptab", "k_jpeg_pcode", "k_jpeg_ppack". */
+#define FI_JPEG_ENC_PROGRESSIVE 1u
+int fi_jpeg_encode_bound_ex(int32_t w, int32_t h, int32_t channels, int32_t quality, int32_t subsampling,
+                            uint32_t flags, size_t *bytes);
+int fi_jpeg_encode_device_ex(fi_ctx *ctx, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                             const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
+                             const int32_t *subsampling, int32_t n, uint8_t *const *out, const size_t *out_cap,
+                             size_t *out_len, int32_t *status, uint32_t flags);
+/* Test hook (not a reference interface): the progressive encoder's host model,
+ * which runs the entropy coder, table builder and file layout the device
+ * kernels run.  coefs: ncoefs quantised coefficients in the layout
+ * fi_debug_jpeg_coefs_host hands out (zigzag int16 blocks, a plane per
+ * component, whole MCUs).  Writes the file to out (out_cap bytes; *out_len =
+ * its size, FI_ENOMEM when it does not fit) and *flushes = how often the
+ * correction-bit buffer ended an EOB run inside a restart interval. */
+int fi_debug_jpeg_prog_write_host(const int16_t *coefs, size_t ncoefs, int32_t w, int32_t h, int32_t channels,
+                                  int32_t quality, int32_t subsampling, uint8_t *out, size_t out_cap,
+                                  size_t *out_len, int32_t *flushes);
 /* GPU PNG encode: the outputs JPEG cannot carry (2 or 4 channels: alpha) leave
  * the device as PNG files -- signature, IHDR (bit depth 8, colour type 0 / 4 /
  * 2 / 6 for 1 / 2 / 3 / 4 channels, no interlace), IDAT chunks, IEND, no

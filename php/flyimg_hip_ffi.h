@@ -63,6 +63,12 @@ int fi_jpeg_orientation(const uint8_t *data, size_t len, int32_t *orientation);
 int fi_jpeg_decode_device_view(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,
                                uint8_t *const *dst, const int64_t *dst_stride, int32_t out_channels,
                                uint32_t flags, const fi_jpeg_view *views, int32_t *status);
+int fi_jpeg_encode_bound_ex(int32_t w, int32_t h, int32_t channels, int32_t quality, int32_t subsampling,
+                            uint32_t flags, size_t *bytes);
+int fi_jpeg_encode_device_ex(fi_ctx *ctx, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                             const int32_t *channels, const int64_t *src_stride, const int32_t *quality,
+                             const int32_t *subsampling, int32_t n, uint8_t *const *out, const size_t *out_cap,
+                             size_t *out_len, int32_t *status, uint32_t flags);
 int fi_png_encode_bound(int32_t w, int32_t h, int32_t channels, size_t *bytes);
 int fi_png_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t *w, const int32_t *h,
                          const int32_t *channels, const int64_t *src_stride, const int32_t *filter, int32_t n,

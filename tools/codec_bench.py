@@ -18,6 +18,16 @@ the size of the restart-marker files against the host encoder's files of the
 same pixels, and -- from one more, event-timed pass -- the three encode
 kernels' fi_kernel_stats times.
 
+--progressive-encode is the A/B of CodecPipeline(gpu_progressive_encode=...)
+alone: the gpu_decode pipeline with its outputs written as baseline files by
+the GPU (gpu_encode), as progressive files with optimal tables by the GPU
+(gpu_progressive_encode), and as progressive files by the host threads
+(Pillow progressive=True), --reps alternating passes after a warm-up pass of
+each: images/s, the host seconds in the encode stage, the bytes per batch, the
+size of the progressive files against the restart-row baseline files of the
+same pixels, the kernels' fi_kernel_stats times from one event-timed pass, and
+--sweep: the two progressive arms at one batch of each listed size per pass.
+
 --oriented is the A/B of CodecPipeline(gpu_orient=...) alone: the same sources
 with an orientation-6 EXIF segment spliced in, --reps alternating passes with
 the switch off (the host threads decode and rotate them) and on (they join
@@ -69,8 +79,14 @@ def main():
                     help="only the A/B of CodecPipeline(gpu_png=...) on RGBA PNG sources")
     ap.add_argument("--gpu-png-decode", action="store_true",
                     help="only the A/B of CodecPipeline(gpu_png_decode=...) on RGBA PNG sources")
-    ap.add_argument("--sweep", default="16,64,256,1024", help="batch sizes of the --gpu-png-decode crossover sweep")
+    ap.add_argument("--progressive-encode", action="store_true",
+                    help="only the A/B of CodecPipeline(gpu_progressive_encode=...): GPU baseline, GPU progressive "
+                         "and host-thread progressive files")
+    ap.add_argument("--sweep", default="16,64,256,1024",
+                    help="batch sizes of the --gpu-png-decode / --progressive-encode crossover sweep")
     a = ap.parse_args()
+    if a.progressive_encode:
+        return progressive_encode_ab(a)
     if a.gpu_png_decode:
         return png_decode_ab(a)
     if a.gpu_png:
@@ -403,6 +419,109 @@ def progressive_ab(a):
     for p in pipes.values():
         p.close()
     ctx.close()
+
+
+def progressive_encode_ab(a):
+    """The encode stage three ways on the bench workload (1080p baseline
+    sources, gpu_decode): GPU baseline files, GPU progressive files, and the
+    host threads writing Pillow's progressive files."""
+    import statistics
+
+    import numpy as np
+    from PIL import Image
+
+    from flyimg_amd import codec
+    from flyimg_amd.runtime import Context
+    from flyimg_amd.synth import synth_rgb
+
+    blobs = []
+    for i in range(8):
+        b = io.BytesIO()
+        Image.fromarray(synth_rgb(1920, 1080, 100 + i)).save(b, "JPEG", quality=90)
+        blobs.append(b.getvalue())
+    ctx = Context(0)
+
+    def host_progressive(pixels, quality=90):  # codec.encode's settings with progressive=True
+        ch = pixels.shape[2] if pixels.ndim == 3 else 1
+        if ch in (2, 4):
+            return plain_encode(pixels, quality)
+        buf = io.BytesIO()
+        Image.fromarray(pixels, "L" if ch == 1 else "RGB").save(
+            buf, "JPEG", quality=int(quality), subsampling=0 if int(quality) >= 90 else 2, progressive=True)
+        return buf.getvalue()
+
+    def spread(v, nd=4):
+        return {"median": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+
+    plain_encode = codec.encode
+
+    def one_pass(key, images, batch):
+        pipe = pipes[key]
+        pipe.process_stats = {"s_encode": 0.0, "raw_bytes": 0, "encoded_bytes": 0}
+        codec.encode = host_progressive if key == "host_progressive" else plain_encode
+        try:
+            t0 = time.perf_counter()
+            done, files = 0, None
+            while done < images:
+                n = min(batch, images - done)
+                files, _ = pipe.process([blobs[(done + k) % len(blobs)] for k in range(n)], [a.options] * n)
+                done += n
+            return done / (time.perf_counter() - t0), dict(pipe.process_stats), files
+        finally:
+            codec.encode = plain_encode
+
+    pipes = {"gpu_baseline": codec.CodecPipeline(ctx, a.threads, gpu_encode=True),
+             "gpu_progressive": codec.CodecPipeline(ctx, a.threads, gpu_encode=True, gpu_progressive_encode=True),
+             "host_progressive": codec.CodecPipeline(ctx, a.threads)}
+    runs, last = {k: [] for k in pipes}, {}
+    for k in pipes:  # warm-up: every shape, every scratch buffer at its size
+        one_pass(k, a.images, a.batch)
+    for _ in range(a.reps):
+        for k in pipes:
+            ips, st, last[k] = one_pass(k, a.images, a.batch)
+            runs[k].append((ips, st))
+    out = {"sources": "1920x1080 q90 (Pillow)", "options": a.options, "batch": a.batch, "threads": a.threads,
+           "images": a.images, "reps": a.reps}
+    nb = (a.images + a.batch - 1) // a.batch
+    for k in pipes:
+        st = runs[k][-1][1]
+        out[k] = {"images_per_s": spread([r[0] for r in runs[k]], 1),
+                  "s_encode": spread([r[1]["s_encode"] for r in runs[k]]),
+                  "file_bytes_per_batch": st["encoded_bytes"] // nb}
+    out["same_pixels"] = all(np.array_equal(codec.decode(f), codec.decode(g))
+                             for f, g in zip(last["gpu_progressive"][:8], last["gpu_baseline"][:8]))
+    out["progressive_over_restart_row_baseline_bytes"] = round(
+        sum(map(len, last["gpu_progressive"])) / sum(map(len, last["gpu_baseline"])), 4)
+    out["gpu_over_host_progressive_bytes"] = round(
+        sum(map(len, last["gpu_progressive"])) / sum(map(len, last["host_progressive"])), 4)
+    ctx.set_timing(1)
+    out["kernel_ms_per_pass"] = {}
+    for key, names in (("gpu_progressive", ("k_jpeg_fdct", "k_jpeg_pstat", "k_jpeg_ptab", "k_jpeg_pcode", "k_jpeg_ppack")),
+                       ("gpu_baseline", ("k_jpeg_fdct", "k_jpeg_henc", "k_jpeg_pack"))):
+        ctx.reset_stats()
+        one_pass(key, a.images, a.batch)
+        out["kernel_ms_per_pass"][key] = {}
+        for name in names:
+            ms, launches, _ = ctx.stats(name)
+            out["kernel_ms_per_pass"][key][name] = {"ms": round(ms, 3), "launches": launches}
+    ctx.set_timing(0)
+    ctx.reset_stats()
+    sweep = {}
+    for bs in [int(x) for x in a.sweep.split(",") if x]:
+        arms = ("host_progressive", "gpu_progressive")
+        r = {k: [] for k in arms}
+        for k in arms:
+            one_pass(k, bs, bs)
+        for _ in range(a.reps):
+            for k in arms:
+                r[k].append(one_pass(k, bs, bs)[0])
+        sweep[str(bs)] = {k: spread(v, 1) for k, v in r.items()}
+        sweep[str(bs)]["gpu_over_host"] = round(statistics.median(r[arms[1]]) / statistics.median(r[arms[0]]), 3)
+    out["sweep_images_per_s"] = sweep
+    for p in pipes.values():
+        p.close()
+    ctx.close()
+    print(json.dumps({"gpu_progressive_encode_ab": out}))
 
 
 def oriented_ab(a):
