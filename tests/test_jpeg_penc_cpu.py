@@ -20,6 +20,7 @@ from flyimg_amd import _lib as L
 from flyimg_amd.runtime import jpeg_coefs_host, jpeg_encode_bound, jpeg_prog_write_host
 from flyimg_amd.synth import synth_rgb
 
+from . import _encoder_content as E
 from .test_jpeg_encode_cpu import GEOMETRIES
 from .test_sanitize_cpu import ENV, ROOT, SAN, _compiler
 
@@ -149,7 +150,14 @@ def test_writer_under_asan_ubsan_matches_pillow():
         px = synth_rgb(w, h, 3 + w)
         cases += [(px, 90, 0), (px, 75, 2), (np.ascontiguousarray(px[..., 1]), 80, 0)]
     noise = np.random.default_rng(3).integers(0, 256, (45, 77, 3), dtype=np.uint8)
-    cases += [(noise, 100, 0), (noise, 100, 2), (synth_rgb(97, 61, 5), 1, 2), (flush_image(), 100, 0)]
+    cases += [(noise, 100, 0), (noise, 100, 2), (synth_rgb(97, 61, 5), 1, 2)]
+    # crafted coefficients (tests/_encoder_content.py): the code-length limit, the refinement scan's
+    # ZRL rules, the largest DC and AC categories, EOB runs of 4094 and 8188
+    crafted = E.crafted()
+    cases += [(c.px, c.quality, c.subsampling) for c in (
+        crafted[n] for n in ("deep17_gray", "zero_runs_gray", "zero_runs_444", "dc_swing_gray", "dc_swing_444",
+                             "dc_swing_420", "ac_max_gray", "ac_max_444", "long_eob_single"))]
+    cases += [(flush_image(), 100, 0)]  # (stays the last one)
     bad = [(10, 10, 4, 90, 0), (10, 10, 3, 0, 0), (0, 5, 1, 50, 0), (10, 10, 3, 90, 1), (16, 16, 3, 90, 0)]
     with tempfile.TemporaryDirectory() as d:
         exe = os.path.join(d, "jpeg_pwrite")
