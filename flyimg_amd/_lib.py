@@ -39,6 +39,8 @@ FI_OP_UNSHARP = 1 << 10
 FI_OP_SHARPEN = 1 << 11
 FI_OP_BLUR = 1 << 12
 FI_SRC_PSEUDOCLASS = 1 << 13  # IM PseudoClass source (palette / gray): Mitchell (resize.c)
+FI_OP_ROTATE_SHEAR = 1 << 14  # with FI_OP_ROTATE: any integer angle (IM's three-shear RotateImage)
+FI_OP_BACKGROUND = 1 << 15  # -background: FiImage.background (0x00RRGGBB) fills what a shear rotation uncovers
 
 GRAVITY = {
     "NorthWest": 1, "North": 2, "NorthEast": 3, "West": 4, "Center": 5,
@@ -54,6 +56,7 @@ class FiImage(ctypes.Structure):
         ("target_w", ctypes.c_int32), ("target_h", ctypes.c_int32),
         ("flags", ctypes.c_uint32), ("gravity", ctypes.c_int32), ("rotate", ctypes.c_int32),
         ("smartcrop_w", ctypes.c_int32), ("smartcrop_h", ctypes.c_int32),
+        ("background", ctypes.c_uint32),  # in the padding before dst: no older field moved
         ("dst", ctypes.c_void_p), ("dst_capacity", ctypes.c_int64),
         ("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32),
         ("out_channels", ctypes.c_int32), ("out_stride", ctypes.c_int32),
@@ -197,6 +200,8 @@ def lib():
     L.fi_query.argtypes = [vp, P(i32)]
     L.fi_debug_monochrome.argtypes = [vp, vp, i32, i32, i32, vp, i32]
     L.fi_debug_convolve.argtypes = [vp, vp, i32, i32, i32, vp, ctypes.c_uint32, vp]
+    L.fi_debug_rotate.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.c_uint32, vp, vp, P(i32), P(i32)]
+    L.fi_debug_rotate_host.argtypes = [vp, i32, i32, i32, i32, ctypes.c_uint32, vp, vp, P(i32), P(i32)]
     L.fi_debug_skinsat.argtypes = [vp, vp, vp]
     L.fi_debug_host_plan.argtypes = [ctypes.POINTER(FiImage), i32, i32, ctypes.POINTER(ctypes.c_double)]
     L.fi_jpeg_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(i32), P(i32), P(i32)]

@@ -193,11 +193,13 @@ class CodecPipeline:
     on such sources, device-resident, 80 against 553 img/s of the host-decode
     arm at batches of 64, 230 against 397 at 256, and 429 against 379 at 1024
     images, where the host arm's spread still reaches past it; DESIGN.md 3.8.  ``decode_stats`` counts the images ``process`` decoded
-    on each side."""
+    on each side.  With ``shear_rotate`` (off by default) ``r_`` by any
+    integer angle and ``bg_`` run on the GPU instead of being
+    rejected."""
 
     def __init__(self, ctx, threads: int = 16, gpu_decode: bool = True, gpu_encode: bool = False,
                  gpu_progressive: bool = False, gpu_orient: bool = False, gpu_png: bool = False,
-                 gpu_png_decode: bool = False, gpu_progressive_encode: bool = False):
+                 gpu_png_decode: bool = False, gpu_progressive_encode: bool = False, shear_rotate: bool = False):
         if gpu_progressive_encode and not gpu_encode:
             raise ValueError("gpu_progressive_encode needs gpu_encode=True: it selects the GPU encoder's file class")
         if gpu_png and not gpu_encode:
@@ -211,6 +213,7 @@ class CodecPipeline:
         self.gpu_png = gpu_png
         self.gpu_png_decode = gpu_png_decode
         self.gpu_progressive_encode = gpu_progressive_encode
+        self.shear_rotate = shear_rotate  # ImageProcessor's opt-in: r_ by any integer angle, bg_
         self.decode_stats = {"gpu": 0, "host": 0}  # images ``process`` decoded on the GPU / on the host
         # ``process``: host seconds in the encode stage, the bytes its outputs
         # were as pixels and are as files (with gpu_encode, what crosses PCIe)
@@ -230,7 +233,7 @@ class CodecPipeline:
         for (img, pseudo), bag in zip(decoded, bags):
             img = ExtractProcessor.extract(bag, img)
             h, w = img.shape[:2]
-            op = ImageProcessor(bag, w, h).to_op()
+            op = ImageProcessor(bag, w, h, shear_rotate=self.shear_rotate).to_op()
             if pseudo:
                 op.flags |= L.FI_SRC_PSEUDOCLASS
             ops.append(op)
@@ -274,7 +277,7 @@ class CodecPipeline:
                     continue
                 w, h = d[0], d[1]
                 views.append((p, w, h, st, chans[i]))
-                op = ImageProcessor(bag, w, h).to_op()
+                op = ImageProcessor(bag, w, h, shear_rotate=self.shear_rotate).to_op()
                 # 1-component JPEG, gray or palette PNG (Pillow's "L" / "P"): IM PseudoClass (Mitchell), as
                 # decode_ex flags it
                 if (d[3] in (0, 3)) if png[i] else (d[2] == 1):
@@ -432,7 +435,7 @@ class CodecPipeline:
             h, w = img.shape[:2]
             q = bag.get_option("quality")
             quality.append(int(q) if not _empty(q) else 90)
-            op = ImageProcessor(bag, w, h).to_op()
+            op = ImageProcessor(bag, w, h, shear_rotate=self.shear_rotate).to_op()
             if pseudo:
                 op.flags |= L.FI_SRC_PSEUDOCLASS
             ops.append(op)

@@ -253,6 +253,102 @@ int fi_debug_convolve(fi_ctx *c, const uint16_t *q16, int32_t w, int32_t h, int3
   return rc;
 }
 
+// Test hook: the rotation stage (fi_rotate.hip) on a caller-supplied Q16 HWC
+// image, planned as plan_im plans it; ctx NULL: the planner's answer only.
+static int debug_rotate(fi_ctx *c, bool host_model, const uint16_t *q16, int32_t w, int32_t h, int32_t ch,
+                        int32_t degrees, uint32_t background, uint16_t *out_q16, uint8_t *out8, int32_t *out_w,
+                        int32_t *out_h) {
+  if (w <= 0 || h <= 0 || (ch != 1 && ch != 3) || !out_w || !out_h) return set_err(FI_EINVAL, "bad arguments");
+  ShearPlan S;
+  plan_rotate_angle(degrees, &S);
+  const int rot = S.rot;
+  const int iw = (rot == 90 || rot == 270) ? h : w, ih = (rot == 90 || rot == 270) ? w : h;
+  *out_w = iw;
+  *out_h = ih;
+  if (S.on) {
+    if (!plan_shear(iw, ih, &S)) return set_err(FI_EUNSUPPORTED, "-rotate: the rotated image is empty or too large");
+    if (!S.contained) return set_err(FI_EUNSUPPORTED, "-rotate: shear leaves IM's canvas (tall, narrow image)");
+    *out_w = S.cw;
+    *out_h = S.ch;
+  }
+  if (!c && !host_model) return FI_OK;
+  if (!q16) return set_err(FI_EINVAL, "bad arguments");
+  // IntegralRotateImage on the host (the resample epilogue's job in a batch)
+  std::vector<uint16_t> I((size_t)iw * ih * ch);
+  for (int y = 0; y < h; y++)
+    for (int x = 0; x < w; x++) {
+      int dx = x, dy = y;
+      if (rot == 90) dx = h - 1 - y, dy = x;
+      if (rot == 180) dx = w - 1 - x, dy = h - 1 - y;
+      if (rot == 270) dx = y, dy = w - 1 - x;
+      for (int k = 0; k < ch; k++) I[((size_t)dy * iw + dx) * ch + k] = q16[((size_t)y * w + x) * ch + k];
+    }
+  const size_t ob = (size_t)*out_w * *out_h * ch;
+  if (!S.on) {
+    if (out_q16) memcpy(out_q16, I.data(), ob * 2);
+    if (out8)
+      for (size_t e = 0; e < ob; e++) out8[e] = (uint8_t)(((I[e] + 128u) - ((I[e] + 128u) >> 8)) >> 8);
+    return FI_OK;
+  }
+  if (host_model) {
+    RotDesc r{};
+    r.src = I.data();
+    r.w = iw, r.h = ih, r.C = ch;
+    r.bx = S.bx, r.by = S.by, r.cols = S.cols, r.rows = S.rows;
+    for (int k = 0; k < 3; k++) r.sh[k] = S.sh[k];
+    r.cx = S.cx, r.cy = S.cy, r.cw = S.cw, r.ch = S.ch;
+    for (int k = 0; k < 3; k++) r.bg[k] = (uint16_t)(257u * ((background >> (16 - 8 * k)) & 255u));
+    r.dst16 = out_q16;
+    r.dst8 = out8;
+    r.stride16 = r.stride8 = (int64_t)S.cw * ch;
+    rot_host(r);
+    return FI_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t qb = I.size() * 2;
+  const size_t o_q = (qb + 255) / 256 * 256, o_8 = o_q + (ob * 2 + 255) / 256 * 256,
+               o_desc = o_8 + (ob + 255) / 256 * 256, o_pre = o_desc + (sizeof(RotDesc) + 255) / 256 * 256,
+               total = o_pre + 256;
+  uint8_t *d = nullptr;
+  HIP_TRY(hipMalloc(&d, total));
+  RotDesc r{};
+  r.src = (const uint16_t *)d;
+  r.w = iw, r.h = ih, r.C = ch;
+  r.bx = S.bx, r.by = S.by, r.cols = S.cols, r.rows = S.rows;
+  for (int k = 0; k < 3; k++) r.sh[k] = S.sh[k];
+  r.cx = S.cx, r.cy = S.cy, r.cw = S.cw, r.ch = S.ch;
+  for (int k = 0; k < 3; k++) r.bg[k] = (uint16_t)(257u * ((background >> (16 - 8 * k)) & 255u));
+  r.dst16 = (uint16_t *)(d + o_q);
+  r.stride16 = (int64_t)S.cw * ch;
+  r.dst8 = d + o_8;
+  r.stride8 = (int64_t)S.cw * ch;
+  const int32_t pre[2] = {0, rot_tiles(S.cw, S.ch)};
+  int rc = FI_OK;
+  if (hipMemcpy(d, I.data(), qb, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d + o_desc, &r, sizeof(r), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d + o_pre, pre, sizeof(pre), hipMemcpyHostToDevice) != hipSuccess) {
+    rc = set_err(FI_EDEVICE, "fi_debug_rotate: upload failed");
+  } else {
+    launch_rot(c->stream, (const RotDesc *)(d + o_desc), (const int32_t *)(d + o_pre), 1, pre[1]);
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess ||
+        (out_q16 && hipMemcpy(out_q16, d + o_q, ob * 2, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (out8 && hipMemcpy(out8, d + o_8, ob, hipMemcpyDeviceToHost) != hipSuccess))
+      rc = set_err(FI_EDEVICE, "fi_debug_rotate: kernel failed");
+  }
+  (void)hipFree(d);
+  return rc;
+}
+
+int fi_debug_rotate(fi_ctx *c, const uint16_t *q16, int32_t w, int32_t h, int32_t ch, int32_t degrees,
+                    uint32_t background, uint16_t *out_q16, uint8_t *out8, int32_t *out_w, int32_t *out_h) {
+  return debug_rotate(c, false, q16, w, h, ch, degrees, background, out_q16, out8, out_w, out_h);
+}
+// The same with the kernel's per-pixel procedure run on the host (no GPU).
+int fi_debug_rotate_host(const uint16_t *q16, int32_t w, int32_t h, int32_t ch, int32_t degrees,
+                         uint32_t background, uint16_t *out_q16, uint8_t *out8, int32_t *out_w, int32_t *out_h) {
+  return debug_rotate(nullptr, true, q16, w, h, ch, degrees, background, out_q16, out8, out_w, out_h);
+}
+
 int fi_plan(fi_image *imgs, int32_t n) {
   if (n < 0 || (n > 0 && !imgs)) return set_err(FI_EINVAL, "bad image array");
   int first = FI_OK;
@@ -323,6 +419,8 @@ int fi_plan_bytes(const fi_image *imgs, int32_t n, int64_t *bytes) {
     }
     bytes[i] = rows * (int64_t)p.W * p.C + (int64_t)p.out_w * p.out_h * p.out_c +
                ((imgs[i].flags & FI_OP_SMARTCROP) ? 16 : 0);
+    // a shear rotation reads the integral Q16 image once and writes the output above
+    if (p.shear.on) bytes[i] += (int64_t)p.iw * p.ih * p.out_c * 2;
   }
   return first;
 }

@@ -8,8 +8,8 @@
 
 using namespace fi;
 
-// Enqueue the batch: resample, convolutions, -monochrome and the smartcrop
-// stage on the main stream (sc_stream is the same stream); the crop apply on
+// Enqueue the batch: resample, shear rotations, convolutions, -monochrome and
+// the smartcrop stage on the main stream (sc_stream is the same stream); the crop apply on
 // ap_stream behind this batch's smartcrop stage, so it runs beside the next
 // batch's resample (FI_APPLY_OVERLAP=0: on the main stream).  ap_tail marks
 // the last apply for the entry points that must not run before it
@@ -95,6 +95,11 @@ static int launch_batch(fi_ctx *c, const Exec &E, const BatchPlan &Bp, const Pac
       hipLaunchKernelGGL(k_rs_v_final, dim3(K.L2b.tiles), dim3(256), 0, c->stream,
                          (const ResizeDesc *)desc_p(K.L2b), pre_p(K.L2b), K.L2b.n, ai, af);
     }
+  }
+  if (K.RL.tiles) {
+    // shear rotations, between the epilogue's integral rotation and the convolutions
+    Timer t(c, "rotate", Bp.rot_bytes);
+    launch_rot(c->stream, (const RotDesc *)desc_p(K.RL), pre_p(K.RL), K.RL.n, K.RL.tiles);
   }
   if (!Bp.conv_items.empty()) {
     Timer t(c, "conv", 0);

@@ -73,6 +73,33 @@ struct ConvStep {
   double gain, thr;      // mode 2: unsharp gain, QuantumRange * threshold
 };
 
+// One image of the rotation stage (fi_rotate.hip): IM 6.9 RotateImage's three
+// shears and CropToFitImage (shear.c) on the integrally rotated Q16 HWC image
+// the resample epilogue leaves in the workspace.  The canvas (BorderImage:
+// cols x rows of background, the image at (bx, by)) exists only as coordinates.
+struct RotShear {              // XShearImage / YShearImage arguments
+  double s;                    // shear.x or shear.y
+  int32_t width, height;       // as IM passes them (an X shear moves `height` rows of `width` pixels)
+  int32_t x_off, y_off;
+};
+struct RotDesc {
+  const uint16_t *src;         // integral image, w * C elements per row
+  int32_t w, h, C;             // C = 1 (gray) or 3
+  int32_t bx, by;              // border
+  int32_t cols, rows;          // canvas
+  RotShear sh[3];              // X, Y, X
+  int32_t cx, cy, cw, ch;      // CropToFitImage's rectangle (CropImage-clipped) = the output
+  uint16_t bg[4];              // background, Q16
+  uint8_t *dst8;               // 8-bit output (ScaleQuantumToChar), or nullptr
+  uint16_t *dst16;             // Q16 output (the convolution stage's input), or nullptr
+  int64_t stride8, stride16;   // bytes / elements per row
+};
+constexpr int kRotTileW = 256;  // output px per tile row: 64 lanes x 4 px
+constexpr int kRotTileH = 4;    // rows per tile: one per wave
+__host__ __device__ inline int rot_tiles(int cw, int ch) {
+  return ((cw + kRotTileW - 1) / kRotTileW) * ((ch + kRotTileH - 1) / kRotTileH);
+}
+
 // smartcrop crop window in the analysed image (smartcrop.py crops()).
 struct DevCrop {
   double fx, fy, fw, fh;  // as Python holds them

@@ -79,6 +79,109 @@ static void gravity_offset(int W, int H, int ew, int eh, int gravity, int *x, in
   *y = (int)oy;
 }
 
+// ---------------------------------------------------------------------------
+// IM 6.9 RotateImage (shear.c): angle reduction, shear constants, BorderImage's
+// canvas, the XShearImage / YShearImage arguments and CropToFitImage
+// ---------------------------------------------------------------------------
+static constexpr double kImPi = 3.14159265358979323846264338327950288419716939937510;  // MagickPI
+void plan_rotate_angle(int degrees, ShearPlan *s) {
+  *s = ShearPlan();
+  double angle = fmod((double)degrees, 360.0);
+  if (angle < -45.0) angle += 360.0;
+  int rotations = 0;
+  for (; angle > 45.0; rotations++) angle -= 90.0;
+  rotations %= 4;
+  s->rot = 90 * rotations;
+  const double rad = kImPi * angle / 180.0;  // DegreesToRadians
+  s->sx = -tan(rad / 2.0);
+  s->sy = sin(rad);
+  s->on = !(s->sx == 0.0 && s->sy == 0.0);
+}
+// IM's scans clip by themselves where a line's step is too large for the
+// canvas: a LEFT / UP line with step > off is skipped, a RIGHT / DOWN line
+// drops the iterations that would write past the canvas.  fi_rotate.hip
+// reproduces both.  What IM does not guard is the RIGHT / DOWN trailer at off +
+// step - 1: past the canvas it leaves the row, and such an image is rejected.
+// The lines k = 0 and nlines - 1 carry the largest step (|d| = |s (k - nlines /
+// 2)| falls towards the middle line).
+static bool shear_contained(double s, int nlines, int ext, int off, int canvas) {
+  if (off < 0 || off + ext > canvas) return false;
+  for (int k : {0, nlines - 1}) {
+    double d = s * ((double)k - nlines / 2.0);
+    if (d == 0.0) continue;
+    const bool right = d > 0.0;
+    if (!right) d *= -1.0;
+    if (d > 1e9) return false;
+    const long step = (long)floor(d) + 1;
+    if (right && off + step > canvas) return false;
+  }
+  return true;
+}
+bool plan_shear(int w, int h, ShearPlan *s) {
+  const double sx = s->sx, sy = s->sy;
+  s->w = w;
+  s->h = h;
+  const double fbw = fabs((double)h * sx) + w + 0.5;
+  if (!(fbw < 1e9)) return false;
+  const long bw = (long)fbw;
+  const double fbh = fabs((double)bw * sy) + h + 0.5;
+  if (!(fbh < 1e9)) return false;
+  const long bh = (long)fbh;
+  const long sw = (long)(fabs((double)bh * sx) + bw + 0.5);
+  const long bx = (long)floor((double)((sw > bw) ? w : bw - sw + 2) / 2.0 + 0.5);
+  const long by = (long)floor(((double)bh - h + 2) / 2.0 + 0.5);
+  const long cols = w + 2 * bx, rows = h + 2 * by;
+  if (bx < 0 || by < 0 || cols > (1 << 30) || rows > (1 << 30)) return false;
+  s->bx = (int)bx;
+  s->by = (int)by;
+  s->cols = (int)cols;
+  s->rows = (int)rows;
+  // (IM computes these offsets in size_t: a canvas narrower than bounds.width
+  // wraps there; here it is simply not contained)
+  s->contained = cols >= bw && rows >= bh && rows >= h;
+  const int xo = (int)((cols - bw) / 2), yo3 = (int)((rows - bh) / 2);
+  s->sh[0] = RotShear{sx, w, h, (int)bx, (int)((rows - h) / 2)};
+  s->sh[1] = RotShear{sy, (int)bw, h, xo, (int)by};
+  s->sh[2] = RotShear{sx, (int)bw, (int)bh, xo, yo3};
+  if (s->contained) {
+    for (int k = 0; k < 3; k++) {
+      const RotShear &q = s->sh[k];
+      const bool ok = k == 1 ? (q.x_off >= 0 && q.x_off + q.width <= s->cols &&
+                                shear_contained(q.s, q.width, q.height, q.y_off, s->rows))
+                             : (q.y_off >= 0 && q.y_off + q.height <= s->rows &&
+                                shear_contained(q.s, q.height, q.width, q.x_off, s->cols));
+      s->contained = s->contained && ok;
+    }
+  }
+  // CropToFitImage(rotate = MagickTrue), then CropImage's clip to the canvas
+  double minx = 0, miny = 0, maxx = 0, maxy = 0;
+  for (int i = 0; i < 4; i++) {
+    double x = (i & 1) ? (double)w / 2.0 : (double)(-(double)w / 2.0);
+    double y = (i & 2) ? (double)h / 2.0 : (double)(-(double)h / 2.0);
+    x += sx * y;
+    y += sy * x;
+    x += sx * y;
+    x += (double)cols / 2.0;
+    y += (double)rows / 2.0;
+    if (i == 0 || x < minx) minx = x;
+    if (i == 0 || x > maxx) maxx = x;
+    if (i == 0 || y < miny) miny = y;
+    if (i == 0 || y > maxy) maxy = y;
+  }
+  long cx = (long)ceil(minx - 0.5), cy = (long)ceil(miny - 0.5);
+  long cw = (long)floor(maxx - minx + 0.5), ch = (long)floor(maxy - miny + 0.5);
+  if (cx < 0) cw += cx, cx = 0;
+  if (cy < 0) ch += cy, cy = 0;
+  if (cx + cw > cols) cw = cols - cx;
+  if (cy + ch > rows) ch = rows - cy;
+  if (cw <= 0 || ch <= 0) return false;
+  s->cx = (int)cx;
+  s->cy = (int)cy;
+  s->cw = (int)cw;
+  s->ch = (int)ch;
+  return true;
+}
+
 int plan_im(const fi_image &img, ImPlan *p) {
   *p = ImPlan();
   p->W = img.src_w;
@@ -147,8 +250,21 @@ int plan_im(const fi_image &img, ImPlan *p) {
   p->gray = (f & FI_OP_GRAY) != 0 || p->mono;
   p->rot = 0;
   if (f & FI_OP_ROTATE) {
-    if (img.rotate % 90) return fail(FI_EUNSUPPORTED, "only -rotate by multiples of 90 (IntegralRotateImage)");
-    p->rot = ((img.rotate % 360) + 360) % 360;
+    if ((img.rotate % 90) && (f & FI_OP_ROTATE_SHEAR)) {
+      plan_rotate_angle(img.rotate, &p->shear);
+      p->rot = p->shear.rot;
+    } else {
+      if (img.rotate % 90) return fail(FI_EUNSUPPORTED, "only -rotate by multiples of 90 (IntegralRotateImage)");
+      p->rot = ((img.rotate % 360) + 360) % 360;
+    }
+  }
+  if (matte && (f & FI_OP_BACKGROUND)) return fail(FI_EUNSUPPORTED, "-background of an RGBA image is not on the GPU path");
+  if (f & FI_OP_BACKGROUND) p->bg = img.background & 0xFFFFFFu;
+  if (p->shear.on) {
+    if (matte) return fail(FI_EUNSUPPORTED, "-rotate by a non-multiple of 90 of an RGBA image is not on the GPU path");
+    if (p->mono) return fail(FI_EUNSUPPORTED, "-rotate by a non-multiple of 90 of a -monochrome image is not on the GPU path");
+    if (p->gray && ((p->bg >> 16) != ((p->bg >> 8) & 255u) || (p->bg >> 16) != (p->bg & 255u)))
+      return fail(FI_EUNSUPPORTED, "-rotate of a Gray image with a coloured -background is not on the GPU path");
   }
   if (matte && p->mono) return fail(FI_EUNSUPPORTED, "-monochrome of an RGBA source is not on the GPU path");
   if (matte && (f & FI_OP_SMARTCROP))
@@ -174,8 +290,14 @@ int plan_im(const fi_image &img, ImPlan *p) {
       return fail(FI_EUNSUPPORTED, "-blur kernel wider than the GPU path supports");
   }
   const bool swap = p->rot == 90 || p->rot == 270;
-  p->out_w = swap ? p->eh : p->ew;
-  p->out_h = swap ? p->ew : p->eh;
+  p->out_w = p->iw = swap ? p->eh : p->ew;
+  p->out_h = p->ih = swap ? p->ew : p->eh;
+  if (p->shear.on) {
+    if (!plan_shear(p->iw, p->ih, &p->shear)) return fail(FI_EUNSUPPORTED, "-rotate: the rotated image is empty or too large");
+    if (!p->shear.contained) return fail(FI_EUNSUPPORTED, "-rotate: shear leaves IM's canvas (tall, narrow image)");
+    p->out_w = p->shear.cw;
+    p->out_h = p->shear.ch;
+  }
   return FI_OK;
 }
 

@@ -14,6 +14,24 @@ namespace fi {
 
 enum Filter { kFilterLanczos = 1, kFilterMitchell = 2 };
 
+// IM 6.9 RotateImage (shear.c) past the integral rotation: the three shears'
+// arguments, BorderImage's canvas and CropToFitImage's rectangle for a w x h
+// integral image, all in f64 in IM's evaluation order.
+struct ShearPlan {
+  bool on = false;             // false: the angle reduces to a multiple of 90 (IntegralRotateImage alone)
+  int rot = 0;                 // the integral part: 0 / 90 / 180 / 270
+  double sx = 0, sy = 0;       // shear.x = -tan(angle / 2), shear.y = sin(angle)
+  int w = 0, h = 0;            // integral image
+  int bx = 0, by = 0, cols = 0, rows = 0;
+  RotShear sh[3];
+  int cx = 0, cy = 0, cw = 0, ch = 0;
+  bool contained = true;       // IM's scans never index outside the canvas (else: rejected)
+};
+// degrees -> integral part + shear constants (RotateImage's angle reduction)
+void plan_rotate_angle(int degrees, ShearPlan *s);
+// the rest, for the w x h image after the integral rotation; false: the crop is empty
+bool plan_shear(int w, int h, ShearPlan *s);
+
 // Resample geometry of one image, ImageMagick 6 semantics.
 struct ImPlan {
   int status = FI_OK;
@@ -34,6 +52,11 @@ struct ImPlan {
   // forwarded convolutions on the rotated Q16 image (bit 0 unsharp, 1 sharpen, 2 blur)
   unsigned conv = 0;
   double cv[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // unsharp r, s, gain, thr; sharpen r, s; blur r, s
+  // FI_OP_ROTATE_SHEAR: the shear rotation of the integrally rotated image;
+  // out_w x out_h is then its crop, iw x ih the integral image
+  ShearPlan shear;
+  int iw = 0, ih = 0;
+  uint32_t bg = 0xFFFFFFu;     // -background 0x00RRGGBB (IM's default: white)
 };
 int plan_im(const fi_image &img, ImPlan *p);
 // IM 6.9 kernels of the forwarded convolutions (morphology.c BlurKernel,

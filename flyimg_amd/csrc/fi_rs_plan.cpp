@@ -4,7 +4,7 @@
 // the whole of it, for run_batch and for the host-only hook alike.
 //   plan_image (per image: geometry, descriptor, resample path + tables)
 //   -> plan_batch_sc (smartcrop stage) -> resolve_workspace (device pointers,
-//   -monochrome / convolution steps, crop apply) -> build_vm_tiles (k_rs_vr /
+//   rotation / -monochrome / convolution steps, crop apply) -> build_vm_tiles (k_rs_vr /
 //   k_rs_vm) / build_hv_tiles (fi_tiles.cpp) -> pack_batch (one blob)
 #include "fi_runtime.h"
 
@@ -105,7 +105,7 @@ static int64_t plan_resample(fi_ctx *c, Exec &E, BatchPlan &Bp, const ImPlan &P,
   const AxisTable *vt = add_axis(c, E, P.filter, P.yf, P.sh, P.th, P.ey0, P.ey0 + P.eh, P.sample, P.H, &d.v, Bp.placed);
   const AxisTable *ht = add_axis(c, E, P.filter, P.xf, P.sw, P.tw, P.ex0, P.ex0 + P.ew, P.sample, P.W, &d.h, Bp.placed);
   const bool rgb = P.C == 3;
-  const bool fast_ok = rgb && !P.conv;  // the streaming kernels write 8-bit only
+  const bool fast_ok = rgb && !P.conv && !P.shear.on;  // the streaming kernels write 8-bit only
   if (!rgb) {
     // matte (RGBA) images: the alpha-weighted f64 generic passes (k_rs4_*)
     add_axis_f64(c, E, vt, &d.v);
@@ -236,8 +236,8 @@ static void plan_image(fi_ctx *c, Exec &E, BatchPlan &Bp, int i) {
   d.ey0 = P.ey0;
   d.gray = P.gray;
   d.rot = P.rot;
-  d.out_w = P.out_w;
-  d.out_h = P.out_h;
+  d.out_w = P.iw;  // (the integral rotation's dims: a shear rotation follows it in its own stage)
+  d.out_h = P.ih;
   d.out_c = P.out_c;
   d.dst_stride = im.out_stride;
   Bp.res_stride[i] = im.out_stride;
@@ -280,6 +280,20 @@ static void plan_image(fi_ctx *c, Exec &E, BatchPlan &Bp, int i) {
     d.dst = (uint8_t *)(uintptr_t)(ci.a_off + 1);
     d.dst_stride = (int64_t)P.out_w * P.out_c * 2;
     d.q16out = 1;
+  }
+  if (P.shear.on) {
+    // the epilogue writes the integrally rotated Q16 image; fi_rotate.hip
+    // shears it into the 8-bit output (dst or the apply's workspace copy) or
+    // into the convolutions' first Q16 buffer
+    RotItem ri;
+    ri.img = i;
+    ri.q_off = E.work.take((size_t)P.iw * P.ih * P.out_c * 2);
+    ri.conv = P.conv ? (int)Bp.conv_items.size() - 1 : -1;
+    Bp.rot_items.push_back(ri);
+    d.dst = (uint8_t *)(uintptr_t)(ri.q_off + 1);
+    d.dst_stride = (int64_t)P.iw * P.out_c * 2;
+    d.q16out = 1;
+    Bp.rot_bytes += (double)P.iw * P.ih * P.out_c * 2 + (double)need * (P.conv ? 2 : 1);
   }
   int64_t src_bytes;
   if (!P.resize) {
@@ -352,6 +366,26 @@ static void resolve_workspace(Exec &E, BatchPlan &Bp, uint8_t *wb) {
     md.st = (MonoState *)(wb + m.st_off);
     Bp.mdesc_mono.push_back(md);
   }
+  for (const RotItem &ri : Bp.rot_items) {
+    const ImPlan &P = Bp.plans[ri.img];
+    const ShearPlan &S = P.shear;
+    RotDesc r{};
+    r.src = (const uint16_t *)(wb + ri.q_off);
+    r.w = S.w, r.h = S.h, r.C = P.out_c;
+    r.bx = S.bx, r.by = S.by, r.cols = S.cols, r.rows = S.rows;
+    for (int k = 0; k < 3; k++) r.sh[k] = S.sh[k];
+    r.cx = S.cx, r.cy = S.cy, r.cw = S.cw, r.ch = S.ch;
+    // Q16 = 257 * the 8-bit channel (ScaleCharToQuantum); Gray: R = G = B (plan_im)
+    for (int k = 0; k < 3; k++) r.bg[k] = (uint16_t)(257u * ((P.bg >> (16 - 8 * k)) & 255u));
+    if (ri.conv >= 0) {
+      r.dst16 = (uint16_t *)(wb + Bp.conv_items[ri.conv].a_off);
+      r.stride16 = (int64_t)P.out_w * P.out_c;
+    } else {
+      r.dst8 = Bp.out_of[ri.img];
+      r.stride8 = Bp.res_stride[ri.img];
+    }
+    Bp.rdesc_rot.push_back(r);
+  }
   for (const ConvItem &ci : Bp.conv_items) {
     const ImPlan &P = Bp.plans[ci.img];
     uint16_t *A = (uint16_t *)(wb + ci.a_off), *Bf = (uint16_t *)(wb + ci.b_off);
@@ -417,8 +451,8 @@ static void resolve_workspace(Exec &E, BatchPlan &Bp, uint8_t *wb) {
     ApplyDesc a{};
     a.src = Bp.out_of[i];
     a.src_stride = Bp.res_stride[i];
-    a.W = d.out_w;
-    a.H = d.out_h;
+    a.W = Bp.plans[i].out_w;
+    a.H = Bp.plans[i].out_h;
     a.C = d.out_c;
     a.result = Bp.sc_of[i];
     a.crop0 = Bp.SL.descs[Bp.sc_of[i]].crop0;
@@ -475,6 +509,11 @@ static void pack_batch(fi_ctx *c, Exec &E, BatchPlan &Bp, Packed &K) {
     std::vector<int> all(Bp.cst[k].size());
     for (size_t j = 0; j < all.size(); j++) all[j] = (int)j;
     K.CL[k] = add_launch(B, Bp.cst[k], all, [](const ConvStep &st) { return st.H; });
+  }
+  if (!Bp.rdesc_rot.empty()) {  // (nothing is placed for a batch without a sheared image)
+    std::vector<int> all(Bp.rdesc_rot.size());
+    for (size_t j = 0; j < all.size(); j++) all[j] = (int)j;
+    K.RL = add_launch(B, Bp.rdesc_rot, all, [](const RotDesc &r) { return rot_tiles(r.cw, r.ch); });
   }
   if (!Bp.mono.empty() && c->mono_wts_at >= 0) K.mono_wts = (size_t)c->mono_wts_at;
   if (!Bp.mono.empty() && c->mono_wts_at < 0) {

@@ -102,6 +102,9 @@ int launch_rs4(hipStream_t s, int mode, const ResizeDesc *d1, const int32_t *p1,
                const ResizeDesc *d2, const int32_t *p2, int n2, int tiles2, const int32_t *ai, const double *ad);
 int launch_rs_h_tile(hipStream_t s, const ResizeDesc *descs, const int32_t *prefix, int n, int tiles,
                      const int32_t *ai, const float *af, int pitch, int taps);
+// shear rotation (fi_rotate.hip)
+int launch_rot(hipStream_t s, const RotDesc *descs, const int32_t *prefix, int n, int tiles);
+void rot_host(const RotDesc &D);  // the kernel's per-pixel procedure on the host (host pointers)
 // -monochrome (fi_mono.hip)
 size_t mono_lds_bytes();
 int launch_mono(hipStream_t s, const MonoDesc *descs, int n, const double *wts);
@@ -532,6 +535,11 @@ struct ConvItem {
   int img;
   size_t a_off, b_off;
 };
+struct RotItem {   // a sheared image: the integral Q16 image in the workspace
+  int img;
+  size_t q_off;
+  int conv;        // index into conv_items when convolutions follow, else -1
+};
 // Everything a batch plans before it is packed and uploaded.
 struct BatchPlan {
   fi_image *imgs = nullptr;
@@ -560,7 +568,8 @@ struct BatchPlan {
   std::vector<uint8_t *> out_of;  // per image: the final 8-bit output (dst, or the workspace +1-tagged)
   std::vector<MonoItem> mono;
   std::vector<ConvItem> conv_items;
-  double resize_bytes = 0;
+  std::vector<RotItem> rot_items;
+  double resize_bytes = 0, rot_bytes = 0;
   // smartcrop stage
   ScLaunchData SL;
   std::vector<int> sstatus;
@@ -570,6 +579,7 @@ struct BatchPlan {
   std::vector<MonoDesc> mdesc_mono;
   std::vector<ConvStep> cst[6];  // U-H, U-V+combine, S-2D, B-H, B-V, to8
   std::vector<ApplyDesc> apply;
+  std::vector<RotDesc> rdesc_rot;
   // tiles
   std::vector<VDesc> vdescs;
   std::vector<MStrip> vstrips;
@@ -596,6 +606,7 @@ struct Packed {
   size_t hdesc_off = 0, hstrip_off = 0, htile_off = 0;
   size_t ai_off = 0, af_off = 0, ad_off = 0, mono_wts = 0;
   Launch L0, L1a, L2a, L2b, Q0, Q1a, Q2a, Q2b, CL[6];
+  Launch RL;  // the rotation stage (placed only when the batch has a sheared image)
   bool h_tiled = false;
   ScLaunches SX;
 };

@@ -67,6 +67,37 @@ def _empty(v) -> bool:
     return v is None or v is False or v == "" or v == "0" or v == 0
 
 
+# -background colours the GPU path takes (IM's names for them, color.c)
+BACKGROUND_NAMES = {
+    "white": 0xFFFFFF, "black": 0x000000, "red": 0xFF0000, "lime": 0x00FF00, "blue": 0x0000FF,
+    "yellow": 0xFFFF00, "cyan": 0x00FFFF, "aqua": 0x00FFFF, "magenta": 0xFF00FF, "fuchsia": 0xFF00FF,
+}
+
+
+def parse_background(text) -> int:
+    """A ``-background`` value as 0x00RRGGBB: ``#rgb``, ``#rrggbb``,
+    ``rgb(r,g,b)`` with 0-255 integers, or one of BACKGROUND_NAMES
+    (case-insensitive).  Everything else -- alpha forms, percentages, other
+    names -- is not on the GPU path."""
+    import re
+
+    t = str(text).strip()
+    m = re.fullmatch(r"#([0-9a-fA-F]{3})", t)
+    if m:
+        r, g, b = (int(ch * 2, 16) for ch in m.group(1))
+        return (r << 16) | (g << 8) | b
+    m = re.fullmatch(r"#([0-9a-fA-F]{6})", t)
+    if m:
+        return int(m.group(1), 16)
+    m = re.fullmatch(r"rgb\(\s*([0-9]{1,3})\s*,\s*([0-9]{1,3})\s*,\s*([0-9]{1,3})\s*\)", t, flags=re.I)
+    if m and all(int(v) <= 255 for v in m.groups()):
+        r, g, b = (int(v) for v in m.groups())
+        return (r << 16) | (g << 8) | b
+    if t.lower() in BACKGROUND_NAMES:
+        return BACKGROUND_NAMES[t.lower()]
+    raise ExecFailedException(f"-background {text} is not on the GPU path")
+
+
 class OptionsBag:
     """OptionsBag.php:40-172."""
 
@@ -120,8 +151,11 @@ class ImageProcessor:
 
     FORWARDED = ["background", "rotate", "unsharp", "sharpen", "blur", "filter"]
 
-    def __init__(self, options: OptionsBag, src_w: int, src_h: int):
+    def __init__(self, options: OptionsBag, src_w: int, src_h: int, shear_rotate: bool = False):
         self.options = options
+        # opt-in: -rotate by any integer angle and -background on the GPU
+        # (FI_OP_ROTATE_SHEAR / FI_OP_BACKGROUND); off, both are rejected
+        self.shear_rotate = shear_rotate
         self.src_w, self.src_h = src_w, src_h  # ImageMetaInfo::dimensions() (identify)
         self.geometry = {}
 
@@ -216,12 +250,18 @@ class ImageProcessor:
         rot = o.get_option("rotate")
         if not _empty(rot):
             deg = int(float(rot))
-            if deg % 90:
+            if self.shear_rotate and float(rot) != deg:
+                raise ExecFailedException(f"-rotate {rot} (fractional degrees) is not on the GPU path")
+            if deg % 90 and not self.shear_rotate:
                 raise ExecFailedException(f"-rotate {rot} (non-integral) is not on the GPU path")
             op.flags |= L.FI_OP_ROTATE
+            if self.shear_rotate:
+                op.flags |= L.FI_OP_ROTATE_SHEAR
             op.rotate = deg
         if not _empty(o.get_option("background")):
-            raise ExecFailedException("-background is not on the GPU path")
+            if not self.shear_rotate:
+                raise ExecFailedException("-background is not on the GPU path")
+            op.background = parse_background(o.get_option("background"))
         # forwarded convolutions (:303-315), applied after -rotate in this order
         v = o.get_option("unsharp")
         if not _empty(v):
@@ -308,15 +348,16 @@ class FaceDetectProcessor:
         return image
 
 
-def process_new_image(ctx, options: str, image, pseudo_class: bool = False):
+def process_new_image(ctx, options: str, image, pseudo_class: bool = False, shear_rotate: bool = False):
     """ImageHandler::processNewImage for the GPU path: ExtractProcessor ->
     ImageProcessor -> SmartCropProcessor on one decoded RGB8 image
     (``pseudo_class``: IM would have read a palette / gray PseudoClass image,
-    codec.decode_ex).  Returns (pixels, record)."""
+    codec.decode_ex; ``shear_rotate``: take ``r_`` by any integer angle and
+    ``bg_``, ImageProcessor's opt-in).  Returns (pixels, record)."""
     bag = OptionsBag(options)
     image = ExtractProcessor.extract(bag, image)
     h, w = image.shape[:2]
-    op = ImageProcessor(bag, w, h).to_op()
+    op = ImageProcessor(bag, w, h, shear_rotate=shear_rotate).to_op()
     if pseudo_class:
         op.flags |= L.FI_SRC_PSEUDOCLASS
     outs, recs, rc = ctx.process([image], [op])

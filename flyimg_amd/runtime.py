@@ -31,6 +31,8 @@ class Op:
     unsharp: tuple = (0.0, 1.0, 1.0, 0.05)
     sharpen: tuple = (0.0, 1.0)
     blur: tuple = (0.0, 1.0)
+    # -background 0x00RRGGBB (FI_OP_BACKGROUND); -1: not given (IM's white)
+    background: int = -1
 
 
 def _fill(img: L.FiImage, op: Op):
@@ -42,6 +44,9 @@ def _fill(img: L.FiImage, op: Op):
     for k in range(2):
         img.sharpen[k] = op.sharpen[k]
         img.blur[k] = op.blur[k]
+    if op.background >= 0:
+        img.background = op.background & 0xFFFFFF
+        img.flags |= L.FI_OP_BACKGROUND
 
 
 def plan(width: int, height: int, op: Op):
@@ -746,6 +751,25 @@ class Context:
         L.check(self._lib.fi_debug_monochrome(self.h, g.ctypes.data, w, h, rot, out.ctypes.data, ow))
         return out
 
+    def rotate_q16(self, q16: np.ndarray, degrees: int, background: int = 0xFFFFFF):
+        """Test hook: the rotation stage on a Q16 HWC (or HW gray) image
+        (fi_debug_rotate): ``-background`` 0x00RRGGBB, ``-rotate degrees``.
+        Returns (Q16 result, its 8-bit form)."""
+        q = np.ascontiguousarray(q16, dtype=np.uint16)
+        h, w = q.shape[:2]
+        ch = q.shape[2] if q.ndim == 3 else 1
+        size = rotated_size(w, h, degrees)
+        if size is None:
+            raise L.FiError(L.FI_EUNSUPPORTED, "-rotate: shear leaves IM's canvas")
+        ow, oh = size
+        shape = (oh, ow, ch) if q.ndim == 3 else (oh, ow)
+        o16, o8 = np.zeros(shape, np.uint16), np.zeros(shape, np.uint8)
+        rw, rh = ctypes.c_int32(), ctypes.c_int32()
+        L.check(self._lib.fi_debug_rotate(self.h, q.ctypes.data, w, h, ch, degrees, background & 0xFFFFFF,
+                                          o16.ctypes.data, o8.ctypes.data, ctypes.byref(rw), ctypes.byref(rh)))
+        assert (rw.value, rh.value) == (ow, oh)
+        return o16, o8
+
     def convolve_q16(self, q16: np.ndarray, conv, ops: int) -> np.ndarray:
         """Test hook: the forwarded convolution kernels on a Q16 HWC image
         (fi_debug_convolve); conv = unsharp[4] + sharpen[2] + blur[2]."""
@@ -756,6 +780,37 @@ class Context:
         out = np.zeros(q.shape, np.uint8)
         L.check(self._lib.fi_debug_convolve(self.h, q.ctypes.data, w, h, ch, cv, ops, out.ctypes.data))
         return out
+
+
+def rotated_size(w: int, h: int, degrees: int):
+    """fi_debug_rotate's planner half (no GPU): (out_w, out_h) of a w x h image
+    after ``-rotate degrees``, or None where a shear would leave IM's canvas
+    (FI_EUNSUPPORTED: tall, narrow images)."""
+    ow, oh = ctypes.c_int32(), ctypes.c_int32()
+    rc = L.lib().fi_debug_rotate(None, None, w, h, 3, degrees, 0xFFFFFF, None, None, ctypes.byref(ow),
+                                 ctypes.byref(oh))
+    if rc == L.FI_EUNSUPPORTED:
+        return None
+    L.check(rc)
+    return ow.value, oh.value
+
+
+def rotate_q16_host(q16: np.ndarray, degrees: int, background: int = 0xFFFFFF):
+    """fi_debug_rotate_host (test hook, no GPU): the rotation kernel's
+    per-pixel procedure run on the CPU -- what ``Context.rotate_q16`` returns."""
+    q = np.ascontiguousarray(q16, dtype=np.uint16)
+    h, w = q.shape[:2]
+    ch = q.shape[2] if q.ndim == 3 else 1
+    size = rotated_size(w, h, degrees)
+    if size is None:
+        raise L.FiError(L.FI_EUNSUPPORTED, "-rotate: shear leaves IM's canvas")
+    ow, oh = size
+    shape = (oh, ow, ch) if q.ndim == 3 else (oh, ow)
+    o16, o8 = np.zeros(shape, np.uint16), np.zeros(shape, np.uint8)
+    rw, rh = ctypes.c_int32(), ctypes.c_int32()
+    L.check(L.lib().fi_debug_rotate_host(q.ctypes.data, w, h, ch, degrees, background & 0xFFFFFF, o16.ctypes.data,
+                                         o8.ctypes.data, ctypes.byref(rw), ctypes.byref(rh)))
+    return o16, o8
 
 
 def device_count() -> int:

@@ -70,6 +70,14 @@ extern "C" {
  * 1-component JPEG -- IM's readers give them a colormap): ResizeImage's
  * default filter is then Mitchell, not Lanczos (resize.c). */
 #define FI_SRC_PSEUDOCLASS (1u << 13)
+/* -rotate by any integer number of degrees (opt-in): with FI_OP_ROTATE, the part
+ * of `rotate` that is no multiple of 90 runs IM's RotateImage three-shear
+ * rotation (shear.c) after the integral rotation.  Opaque RGB / Gray images
+ * only; without this flag such an angle is FI_EUNSUPPORTED, as it always was. */
+#define FI_OP_ROTATE_SHEAR (1u << 14)
+/* -background: `background` (0x00RRGGBB) fills what a shear rotation uncovers;
+ * without the flag IM's default, white.  No effect without a shear rotation. */
+#define FI_OP_BACKGROUND (1u << 15)
 
 /* ImageMagick GravityType values used by -gravity (parameters.yml:99). */
 #define FI_GRAVITY_NORTHWEST 1
@@ -96,9 +104,12 @@ typedef struct fi_image {
   int32_t target_h;        /* geometry H (0 = absent)                         */
   uint32_t flags;          /* FI_OP_* | FI_GEOM_*                             */
   int32_t gravity;         /* FI_GRAVITY_*, 0 = Center                        */
-  int32_t rotate;          /* degrees for FI_OP_ROTATE (multiple of 90)       */
+  int32_t rotate;          /* degrees for FI_OP_ROTATE (multiple of 90, or    *
+                            * any integer with FI_OP_ROTATE_SHEAR)            */
   int32_t smartcrop_w;     /* smartcrop.py --width  (0 = 100, CLI default)    */
   int32_t smartcrop_h;     /* smartcrop.py --height (0 = 100)                 */
+  uint32_t background;     /* 0x00RRGGBB, read only with FI_OP_BACKGROUND (in  *
+                            * what was the padding before dst: no field moved) */
   uint8_t *dst;            /* output pixels, HWC, out_stride bytes per row    */
   int64_t dst_capacity;    /* bytes available at dst                          */
   /* ---- filled by library ---- */
@@ -168,7 +179,7 @@ void fi_destroy(fi_ctx *ctx);
 int fi_plan(fi_image *imgs, int32_t n);
 /* Per-image algorithmic HBM bytes of the hot path (SURVEY.md 8(d)/(e)
  * B_img = R_touched * W_in * C_in + out_w * out_h * out_c + 16 when
- * FI_OP_SMARTCROP), R_touched = source rows with a non-zero vertical tap
+ * FI_OP_SMARTCROP, + the integral Q16 image a shear rotation reads), R_touched = source rows with a non-zero vertical tap
  * after the ThumbnailImage sample step.  The multi-GPU sharder balances
  * these (greedy LPT).  bytes[i] = -1 for an image that does not plan. */
 int fi_plan_bytes(const fi_image *imgs, int32_t n, int64_t *bytes);
@@ -251,7 +262,7 @@ int fi_fill_synthetic(fi_ctx *ctx, uint8_t *dev, int32_t w, int32_t h, int32_t s
                       uint32_t seed);
 
 /* Stage timing (HIP event ranges on the launch streams).  enable: 0 off, 1
- * every stage ("batch", "resize", "sc_prep", "sc_score", "crop_apply", "mono",
+ * every stage ("batch", "resize", "rotate", "sc_prep", "sc_score", "crop_apply", "mono",
  * "conv", "h2d_src", "d2h_out"), 2 the resample stage only (each event range
  * adds a few microseconds between dependent kernels).  fi_kernel_stats also
  * reports host timings ("host_*", "host_total") and per-path image counters
@@ -298,6 +309,20 @@ int fi_debug_convolve(fi_ctx *ctx, const uint16_t *q16, int32_t w, int32_t h, in
                       uint32_t ops, uint8_t *out);
 int fi_debug_monochrome(fi_ctx *ctx, const uint16_t *gray, int32_t w, int32_t h, int32_t rot, uint8_t *out,
                         int32_t out_stride);
+/* Test hook (not a reference interface): the rotation stage (fi_rotate.hip) on
+ * a caller-supplied Q16 HWC image (host buffers, ch 1 or 3): -rotate `degrees`
+ * with -background `background` (0x00RRGGBB), the integral part included.
+ * *out_w x *out_h = the rotated image's size; out_q16 (its Q16 pixels) and out8
+ * (ScaleQuantumToChar of them, *out_w * ch bytes per row) may each be NULL.
+ * ctx == NULL: the planner alone -- the size, or FI_EUNSUPPORTED where a shear
+ * would leave IM's canvas -- with no GPU. */
+int fi_debug_rotate(fi_ctx *ctx, const uint16_t *q16, int32_t w, int32_t h, int32_t ch, int32_t degrees,
+                    uint32_t background, uint16_t *out_q16, uint8_t *out8, int32_t *out_w, int32_t *out_h);
+/* Its host model: the per-pixel procedure the kernel runs (taps, blends,
+ * rounding), compiled for the CPU and run over the same arguments with no GPU,
+ * so the CPU suite holds the kernel's arithmetic to the literal restatement. */
+int fi_debug_rotate_host(const uint16_t *q16, int32_t w, int32_t h, int32_t ch, int32_t degrees,
+                         uint32_t background, uint16_t *out_q16, uint8_t *out8, int32_t *out_w, int32_t *out_h);
 /* GPU JPEG decode: the decode step of ImageProcessor's `convert` (IM reads
  * the source with libjpeg; ImageProcessor.php:66-110) moved onto the device,
  * bit-exact with libjpeg-turbo's default decompression (islow IDCT, fancy

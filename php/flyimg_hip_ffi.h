@@ -8,6 +8,7 @@ typedef struct fi_image {
   uint32_t flags;
   int32_t gravity, rotate;
   int32_t smartcrop_w, smartcrop_h;
+  uint32_t background;
   uint8_t *dst;
   int64_t dst_capacity;
   int32_t out_w, out_h, out_channels, out_stride;
