@@ -221,6 +221,10 @@ def lib():
                                                 P(ctypes.c_size_t), P(i32)]
     L.fi_png_encode_bound.argtypes = [i32, i32, i32, P(ctypes.c_size_t)]
     L.fi_png_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.fi_webp_encode_bound.argtypes = [i32, i32, i32, P(ctypes.c_size_t)]
+    L.fi_webp_encode_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.fi_debug_webp_encode_host.argtypes = [vp, i32, i32, i32, ctypes.c_int64, i32, vp, ctypes.c_size_t,
+                                            P(ctypes.c_size_t)]
     L.fi_png_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(i32), P(i32), P(i32), P(i32), P(i32)]
     L.fi_png_decode_device.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     _lib = L

@@ -19,7 +19,9 @@ ImageHandler::processNewImage end to end for a batch of encoded images.
            libjpeg-turbo writes with ``restart_marker_rows=1``.  With
            ``gpu_png`` on top the alpha outputs are written there as well
            (fi_png_encode_device): PNG files of the same pixels, deflated
-           per 32 KiB band on the device.
+           per 32 KiB band on the device.  With ``gpu_webp`` on top the
+           ``o_webp,webpl_1`` outputs leave as lossless WebP
+           (fi_webp_encode_device); otherwise the option is ignored.
 
 Gray (L), bilevel and palette sources are expanded to RGB / RGBA before the
 GPU (IM would keep a gray JPEG gray: the channels are equal either way), and
@@ -173,7 +175,11 @@ class CodecPipeline:
     default, needs ``gpu_encode``) the JPEGs are the file class flyimg ships:
     progressive, with Huffman tables fitted to every scan
     (FI_JPEG_ENC_PROGRESSIVE) -- smaller files, the same decoded pixels,
-    more device time; DESIGN.md 3.6b.  With
+    more device time; DESIGN.md 3.6b.  With ``gpu_webp`` (off by default, needs
+    ``gpu_encode``) the outputs whose options resolve to lossless WebP
+    (``o_webp,webpl_1``), opaque or with alpha, are written by one
+    fi_webp_encode_device call per batch (VP8L; any decoder returns the
+    pixels); without it the option stays ignored.  With
     ``gpu_progressive`` (off by default) progressive JPEG sources join the GPU
     decode batch instead of the host threads (same pixels).  A progressive
     scan is one serial chain on the GPU: measured on 1080p sources the GPU
@@ -199,7 +205,10 @@ class CodecPipeline:
 
     def __init__(self, ctx, threads: int = 16, gpu_decode: bool = True, gpu_encode: bool = False,
                  gpu_progressive: bool = False, gpu_orient: bool = False, gpu_png: bool = False,
-                 gpu_png_decode: bool = False, gpu_progressive_encode: bool = False, shear_rotate: bool = False):
+                 gpu_png_decode: bool = False, gpu_progressive_encode: bool = False, shear_rotate: bool = False,
+                 gpu_webp: bool = False):
+        if gpu_webp and not gpu_encode:
+            raise ValueError("gpu_webp needs gpu_encode=True: the WebP outputs are written by the GPU encode stage")
         if gpu_progressive_encode and not gpu_encode:
             raise ValueError("gpu_progressive_encode needs gpu_encode=True: it selects the GPU encoder's file class")
         if gpu_png and not gpu_encode:
@@ -212,6 +221,7 @@ class CodecPipeline:
         self.gpu_orient = gpu_orient
         self.gpu_png = gpu_png
         self.gpu_png_decode = gpu_png_decode
+        self.gpu_webp = gpu_webp
         self.gpu_progressive_encode = gpu_progressive_encode
         self.shear_rotate = shear_rotate  # ImageProcessor's opt-in: r_ by any integer angle, bg_
         self.decode_stats = {"gpu": 0, "host": 0}  # images ``process`` decoded on the GPU / on the host
@@ -296,15 +306,31 @@ class CodecPipeline:
             full_o[i], full_r[i] = outs[k], recs[k]
         return full_o, full_r, [i for i in range(len(blobs)) if status[i] != L.FI_OK]
 
-    def _gpu_encode(self, outs, quality, held):
+    def _gpu_encode(self, outs, quality, held, webp=None):
         """Every JPEG output in one fi_jpeg_encode_device call: device views
         as they are, host arrays (host-decoded sources) uploaded first; chroma
         as ``encode``: q >= 90 -> 4:4:4, else 4:2:0.  Alpha outputs: host PNG,
-        or with ``gpu_png`` one fi_png_encode_device call for all of them."""
+        or with ``gpu_png`` one fi_png_encode_device call for all of them.
+        ``webp`` (gpu_webp): the outputs that leave as lossless WebP instead,
+        opaque or not, through one fi_webp_encode_device call."""
         encoded = [None] * len(outs)
         views, idx = [], []
         png_views, png_idx = [], []
+        webp_views, webp_idx = [], []
         for i, o in enumerate(outs):
+            if webp and webp[i]:
+                if isinstance(o, tuple):
+                    view = o
+                else:
+                    ch = o.shape[2] if o.ndim == 3 else 1
+                    o = np.ascontiguousarray(o)
+                    p = self.ctx.malloc(max(o.nbytes, 1))
+                    held.append(p)
+                    self.ctx.h2d(p, o)
+                    view = (p, o.shape[1], o.shape[0], o.shape[1] * ch, ch)
+                webp_views.append(view)
+                webp_idx.append(i)
+                continue
             if isinstance(o, tuple):  # a device batch's output; 2 or 4 channels (alpha) from GPU-decoded PNGs
                 view = o
                 if view[4] in (2, 4):
@@ -337,6 +363,12 @@ class CodecPipeline:
                 msg = L.lib().fi_last_error()
                 raise ExecFailedException("Command failed.\nThe exit code: %d\n%s" % (
                     L.FI_EINVAL, msg.decode() if msg else f"image {i}: PNG encode"))
+            encoded[i] = f
+        for i, f in zip(webp_idx, self.ctx.webp_encode(webp_views)):
+            if f is None:
+                msg = L.lib().fi_last_error()
+                raise ExecFailedException("Command failed.\nThe exit code: %d\n%s" % (
+                    L.FI_EINVAL, msg.decode() if msg else f"image {i}: WebP encode"))
             encoded[i] = f
         qs = [int(quality[i]) for i in idx]
         files = self.ctx.jpeg_encode(views, qs, [0 if q >= 90 else 2 for q in qs],
@@ -417,7 +449,10 @@ class CodecPipeline:
         quality = [self._quality(b) for b in bags]
         t0 = time.perf_counter()
         if self.gpu_encode:
-            encoded = self._gpu_encode(outs, quality, held)
+            webp = None
+            if self.gpu_webp:  # o_webp,webpl_1: ImageProcessor.php:199-203 (-define webp:lossless=true)
+                webp = [b.get("output") == "webp" and not _empty(b.get("webp-lossless")) for b in bags]
+            encoded = self._gpu_encode(outs, quality, held, webp)
         else:
             encoded = list(self.pool.map(lambda a: encode(a[0], a[1]), zip(outs, quality)))
         self.process_stats["s_encode"] += time.perf_counter() - t0

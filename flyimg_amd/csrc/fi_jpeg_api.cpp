@@ -4,6 +4,7 @@
 #include "fi_jpeg.h"
 #include "fi_jpeg_enc.h"
 #include "fi_png_enc.h"
+#include "fi_webp_enc.h"
 #include "fi_png_dec.h"
 
 using namespace fi;
@@ -210,6 +211,46 @@ int fi_png_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w,
                      status[i] == FI_EUNSUPPORTED ? "filtered stream beyond 2^31 - 1 bytes"
                      : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
                                                   : "bad PNG source, dimensions, channels or filter");
+  return FI_OK;
+}
+// GPU lossless WebP encode (fi_webp_enc.hip): the PNG encoder's conventions and plumbing
+int fi_webp_encode_bound(int32_t w, int32_t h, int32_t channels, size_t *bytes) {
+  if (!bytes) return set_err(FI_EINVAL, "bad arguments");
+  const int rc = webp_enc_bound(w, h, channels, bytes);
+  if (rc) return set_err(rc, rc == FI_EUNSUPPORTED ? "a side above 16384" : "bad WebP dimensions or channels");
+  return FI_OK;
+}
+int fi_debug_webp_encode_host(const uint8_t *src, int32_t w, int32_t h, int32_t channels, int64_t src_stride,
+                              int32_t predictor, uint8_t *out, size_t out_cap, size_t *out_len) {
+  if (!src || !out_len || (out_cap && !out)) return set_err(FI_EINVAL, "bad arguments");
+  const int rc = webp_encode_host(src, w, h, channels, src_stride, predictor, out, out_cap, out_len);
+  if (rc == FI_ENOMEM) return set_err(rc, "out_cap is below the encoded size (out_len)");
+  if (rc == FI_EDEVICE) return set_err(rc, "WebP encode: the bits emitted differ from the bits priced");
+  if (rc)
+    return set_err(rc, rc == FI_EUNSUPPORTED ? "a side above 16384" : "bad WebP source, dimensions, channels or predictor");
+  return FI_OK;
+}
+int fi_webp_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                          const int32_t *channels, const int64_t *src_stride, const int32_t *predictor, int32_t n,
+                          uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status) {
+  if (!c || n < 0 || (n > 0 && (!src || !w || !h || !channels || !src_stride || !out || !out_cap || !out_len || !status)))
+    return set_err(FI_EINVAL, "bad arguments");
+  if (n == 0) return FI_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
+  std::string err;
+  const int rc = webp_encode_batch(c->stream, src, w, h, channels, src_stride, predictor, n, out, out_cap, out_len,
+                                   status, jpeg_enc_alloc, jpeg_enc_stage, c, &err);
+  jpeg_enc_stage(c, nullptr);
+  collect_timers(c);
+  if (rc) return set_err(rc, "%s", err.c_str());
+  for (int i = 0; i < n; i++)  // the others are encoded
+    if (status[i])
+      return set_err(status[i], "image %d: %s", i,
+                     status[i] == FI_EUNSUPPORTED ? "a side above 16384"
+                     : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
+                                                  : "bad WebP source, dimensions, channels or predictor");
   return FI_OK;
 }
 // GPU PNG decode (fi_png_dec.hip): the sources a JPEG cannot be (alpha, palette); the JPEG

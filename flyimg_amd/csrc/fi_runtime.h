@@ -82,6 +82,11 @@ int png_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w
                      uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status,
                      void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *), void *actx,
                      std::string *err);
+int webp_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                      const int32_t *channels, const int64_t *src_stride, const int32_t *predictor, int n,
+                      uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status,
+                      void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *), void *actx,
+                      std::string *err);
 int png_decode_batch(hipStream_t st, const uint8_t *const *data, const size_t *len, int n, uint8_t *const *dst,
                      const int64_t *dst_stride, const int32_t *out_channels, int32_t *status,
                      void *(*alloc)(void *, int, size_t), void (*stage)(void *, const char *), void *actx,

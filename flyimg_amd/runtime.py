@@ -181,6 +181,30 @@ def png_encode_bound(w: int, h: int, channels: int) -> int:
     return n.value
 
 
+def webp_encode_bound(w: int, h: int, channels: int) -> int:
+    """fi_webp_encode_bound: the true upper bound of the GPU lossless WebP
+    encoder's file size for any image of this geometry (host only); raises
+    FiError for arguments the encoder turns down."""
+    n = ctypes.c_size_t()
+    L.check(L.lib().fi_webp_encode_bound(w, h, channels, ctypes.byref(n)))
+    return n.value
+
+
+def webp_encode_host_form(image: np.ndarray, predictor: int = -1) -> bytes:
+    """fi_debug_webp_encode_host (no GPU): the lossless WebP file of a host
+    array (HW, or HWC with 1..4 channels) from the code the device runs --
+    the device's file, byte for byte."""
+    a = np.ascontiguousarray(image, dtype=np.uint8)
+    h, w = a.shape[:2]
+    c = a.shape[2] if a.ndim == 3 else 1
+    cap = webp_encode_bound(w, h, c)
+    out = np.empty(cap, np.uint8)
+    n = ctypes.c_size_t()
+    L.check(L.lib().fi_debug_webp_encode_host(a.ctypes.data, w, h, c, w * c, predictor, out.ctypes.data, cap,
+                                              ctypes.byref(n)))
+    return out[:n.value].tobytes()
+
+
 def png_info(blob: bytes):
     """fi_png_info: (width, height, channels, colour type, meta) of a PNG file
     the GPU decoder reproduces exactly (8-bit, non-interlaced; channels = the
@@ -653,6 +677,78 @@ class Context:
                 c = a.shape[2] if a.ndim == 3 else 1
                 views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
             return self.png_encode(views, filter)
+        finally:
+            for p in ptrs:
+                self.free(p)
+
+    def _webp_encode_call(self, views, ps, ptrs, caps):
+        n = len(views)
+        I32, I64, SZ, VP = ctypes.c_int32 * n, ctypes.c_int64 * n, ctypes.c_size_t * n, ctypes.c_void_p * n
+        out_len, status = SZ(), I32()
+        rc = self._lib.fi_webp_encode_device(
+            self.h, VP(*[v[0] for v in views]), I32(*[v[1] for v in views]), I32(*[v[2] for v in views]),
+            I32(*[v[4] for v in views]), I64(*[v[3] for v in views]), I32(*ps) if ps is not None else None, n,
+            VP(*ptrs), SZ(*caps), out_len, status)
+        return rc, list(status), list(out_len)
+
+    def _webp_bound(self, view):
+        b = ctypes.c_size_t()
+        return b.value if self._lib.fi_webp_encode_bound(view[1], view[2], view[4], ctypes.byref(b)) == L.FI_OK else 1
+
+    def webp_encode_raw(self, views, predictor=-1, caps=None):
+        """fi_webp_encode_device on (device pointer, w, h, stride, channels)
+        views; ``predictor`` per image, one value for all, or None (the NULL
+        pointer: adaptive); ``caps``: output capacities (default:
+        fi_webp_encode_bound, 1 where the bound turns the image down).
+        Returns (rc, status list, length list, output buffer list) with the
+        0xA5 guards of jpeg_encode_raw."""
+        n = len(views)
+        ps = None if predictor is None else list(predictor) if isinstance(predictor, (list, tuple)) else [predictor] * n
+        if caps is None:
+            caps = [self._webp_bound(v) for v in views]
+        offs = np.concatenate([[0], np.cumsum([c + 64 for c in caps])]).astype(np.int64)
+        pool = np.empty(int(offs[-1]), np.uint8)
+        bufs = [pool[int(offs[i]):int(offs[i + 1])] for i in range(n)]
+        for b, c in zip(bufs, caps):
+            b[max(0, c - 64):] = 0xA5
+        rc, status, lens = self._webp_encode_call(views, ps, [b.ctypes.data for b in bufs], caps)
+        return rc, status, lens, bufs
+
+    def webp_encode(self, views, predictor=-1) -> list[bytes | None]:
+        """fi_webp_encode_device: lossless WebP files of device-resident
+        images given as (device pointer, w, h, stride, channels) views, 1..4
+        channels; any WebP decoder returns the pixels bit for bit.
+        ``predictor``: -1 adaptive, 0..13 fixed (per image or one value).  None
+        where the encoder turned the image down.  The output buffers are sized
+        to fi_webp_encode_bound (below 1 KiB above the pixels), so one call
+        always suffices."""
+        n = len(views)
+        if not n:
+            return []
+        ps = list(predictor) if isinstance(predictor, (list, tuple)) else [predictor] * n
+        caps = [self._webp_bound(v) for v in views]
+        offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+        pool = getattr(self, "_enc_out", None)  # the output pool of jpeg_encode, png_encode and webp_encode alike
+        if pool is None or pool.size < int(offs[-1]):  # kept: fresh pages are the cost of a large buffer
+            pool = self._enc_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
+        base = pool.ctypes.data
+        rc, status, lens = self._webp_encode_call(views, ps, [base + int(o) for o in offs[:-1]], caps)
+        if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL):
+            L.check(rc)  # a failure of the call, not of an image
+        return [pool[int(offs[i]):int(offs[i]) + lens[i]].tobytes() if status[i] == L.FI_OK else None for i in range(n)]
+
+    def webp_encode_host(self, images: list[np.ndarray], predictor=-1) -> list[bytes | None]:
+        """webp_encode of host arrays (HW, HWC with 1..4 channels), uploaded to
+        scratch device buffers first (tests / tools)."""
+        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        ptrs = [self.malloc(max(a.nbytes, 1)) for a in arrs]
+        try:
+            views = []
+            for a, p in zip(arrs, ptrs):
+                self.h2d(p, a)
+                c = a.shape[2] if a.ndim == 3 else 1
+                views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
+            return self.webp_encode(views, predictor)
         finally:
             for p in ptrs:
                 self.free(p)

@@ -486,6 +486,40 @@ int fi_png_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t *
                          const int32_t *channels, const int64_t *src_stride, const int32_t *filter, int32_t n,
                          uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status);
 
+/* GPU lossless WebP encode (opt-in): RIFF / WEBP / VP8L files without a VP8X
+ * chunk or metadata.  1 / 2 / 3 / 4 channels are gray / gray + alpha / RGB /
+ * RGBA (gray replicates into R, G and B; alpha_is_used is set for 2 and 4).
+ * The file carries a subtract-green transform, a predictor transform with one
+ * mode per 16 x 16 block, backward references inside bands of 8192 pixels
+ * (plain distance codes, no colour cache) and one Huffman group.  Lossless:
+ * any decoder returns the source pixels, RGB under alpha 0 included.
+ * fi_webp_encode_bound (host only): a true upper bound of the file size of
+ * any w x h image: the encoder's fallback form (no predictor, no references,
+ * flat 8-bit codes for every channel that varies), w * h * channels bytes plus
+ * a constant header below 1 KiB; the encoder prices both forms and writes the
+ * smaller.
+ * fi_webp_encode_device: encodes n device-resident images src[i] (HWC u8
+ * rows, any src_stride[i] >= w * channels, no alignment assumed) into the host
+ * buffers out[i] of out_cap[i] bytes and waits; out_len[i] = the encoded size.
+ * predictor[i]: -1 = per block the mode (0..13) with the lowest sum of min(x,
+ * 256 - x) over its residual bytes, ties to the lower mode; 0..13 = that mode
+ * on every block; predictor == NULL: -1 for every image.  status[i]: FI_EINVAL
+ * for other channel counts, a side below 1 or a bad predictor, FI_EUNSUPPORTED
+ * for a side above 16384, FI_ENOMEM when out_cap[i] < out_len[i] (nothing is
+ * written past out_cap[i]; out_len[i] is the size needed).  Returns the first
+ * failing status; the other images are encoded.  FI_EDEVICE if what a kernel
+ * emitted differs from what was priced.  Kernel times: "k_webp_pred",
+ * "k_webp_lz", "k_webp_codes", "k_webp_emit", "k_webp_pack" in fi_kernel_stats
+ * (fi_set_timing(1)).
+ * fi_debug_webp_encode_host (no GPU): the same inline code on the CPU; its
+ * file is the specification of the device's file, byte for byte. */
+int fi_webp_encode_bound(int32_t w, int32_t h, int32_t channels, size_t *bytes);
+int fi_webp_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                          const int32_t *channels, const int64_t *src_stride, const int32_t *predictor, int32_t n,
+                          uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status);
+int fi_debug_webp_encode_host(const uint8_t *src, int32_t w, int32_t h, int32_t channels, int64_t src_stride,
+                              int32_t predictor, uint8_t *out, size_t out_cap, size_t *out_len);
+
 /* GPU PNG decode (opt-in): 8-bit, non-interlaced PNG sources of colour type
  * 0 / 2 / 4 / 6, or 3 with a PLTE and an optional tRNS, decoded into device
  * memory bit for bit as Pillow reads them: one 64-lane workgroup inflates an

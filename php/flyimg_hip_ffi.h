@@ -74,6 +74,12 @@ int fi_png_encode_bound(int32_t w, int32_t h, int32_t channels, size_t *bytes);
 int fi_png_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t *w, const int32_t *h,
                          const int32_t *channels, const int64_t *src_stride, const int32_t *filter, int32_t n,
                          uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status);
+int fi_webp_encode_bound(int32_t w, int32_t h, int32_t channels, size_t *bytes);
+int fi_webp_encode_device(fi_ctx *ctx, const uint8_t *const *src, const int32_t *w, const int32_t *h,
+                          const int32_t *channels, const int64_t *src_stride, const int32_t *predictor, int32_t n,
+                          uint8_t *const *out, const size_t *out_cap, size_t *out_len, int32_t *status);
+int fi_debug_webp_encode_host(const uint8_t *src, int32_t w, int32_t h, int32_t channels, int64_t src_stride,
+                              int32_t predictor, uint8_t *out, size_t out_cap, size_t *out_len);
 int fi_png_info(const uint8_t *data, size_t len, int32_t *w, int32_t *h,
                 int32_t *channels, int32_t *color_type, int32_t *meta);
 int fi_png_decode_device(fi_ctx *ctx, const uint8_t *const *data, const size_t *len, int32_t n,

@@ -44,6 +44,15 @@ fi_kernel_stats times from one more event-timed pass, and the sizes -- the GPU
 files against Pillow's default and compress_level=1 files of the same pixels,
 their IDAT payloads against zlib levels 1 and 6 on the same filtered stream.
 
+--gpu-webp compares three ways out for --gpu-png's workload with
+o_webp,webpl_1 appended, in --reps alternating passes after a warm-up pass of
+each: gpu_png (the option ignored, the GPU PNG files), gpu_webp
+(fi_webp_encode_device) and host_webp (the pixels downloaded, --threads
+threads of Pillow save("WEBP", lossless=True, method=0)): images/s, the host
+seconds in the encode stage, the five kernels' times from one more event-timed
+pass, and the GPU WebP files' bytes against libwebp method 0 / 4 / 6 and
+against the GPU PNG files of the same pixels.
+
 --gpu-png-decode is the A/B of CodecPipeline(gpu_png_decode=...) on the same
 RGBA PNG sources and request: --reps alternating passes, after a warm-up pass
 of each, of the host-decode arm with gpu_png (the best arm before the device
@@ -77,6 +86,8 @@ def main():
                     help="only the A/B of CodecPipeline(gpu_orient=...) on orientation-6 sources")
     ap.add_argument("--gpu-png", action="store_true",
                     help="only the A/B of CodecPipeline(gpu_png=...) on RGBA PNG sources")
+    ap.add_argument("--gpu-webp", action="store_true",
+                    help="only the three-arm comparison of CodecPipeline(gpu_webp=...) on RGBA PNG sources")
     ap.add_argument("--gpu-png-decode", action="store_true",
                     help="only the A/B of CodecPipeline(gpu_png_decode=...) on RGBA PNG sources")
     ap.add_argument("--progressive-encode", action="store_true",
@@ -89,6 +100,8 @@ def main():
         return progressive_encode_ab(a)
     if a.gpu_png_decode:
         return png_decode_ab(a)
+    if a.gpu_webp:
+        return webp_ab(a)
     if a.gpu_png:
         return png_ab(a)
     if a.progressive:
@@ -288,6 +301,101 @@ def png_ab(a):
         p.close()
     ctx.close()
     print(json.dumps({"gpu_png_ab": out}))
+
+
+def webp_ab(a):
+    """--gpu-webp: --gpu-png's workload with o_webp,webpl_1 appended, three
+    arms in alternating passes: gpu_png (the GPU PNG files, the option
+    ignored), gpu_webp (fi_webp_encode_device) and host_webp, the host
+    alternative: the pixels downloaded and written by ``threads`` threads of
+    Pillow save("WEBP", lossless=True, method=0)."""
+    import statistics
+
+    import numpy as np
+    from PIL import Image
+
+    from flyimg_amd import codec
+    from flyimg_amd.runtime import Context
+    from flyimg_amd.synth import synth_rgb
+
+    W, H = 1000, 750
+    options = "w_500,o_webp,webpl_1"
+    alpha = ((np.arange(W)[None, :] + 2 * np.arange(H)[:, None]) * 255 // (W + 2 * H)).astype(np.uint8)
+    blobs = []
+    for i in range(8):
+        b = io.BytesIO()
+        Image.fromarray(np.dstack([synth_rgb(W, H, 300 + i), alpha])).save(b, "PNG", compress_level=1)
+        blobs.append(b.getvalue())
+    ctx = Context(0)
+
+    def spread(v):
+        return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+
+    def pillow_webp(px, method=0):
+        b = io.BytesIO()
+        Image.fromarray(px).save(b, "WEBP", lossless=True, method=method)
+        return b.getvalue()
+
+    host_encode = codec.encode
+
+    def one_pass(name):
+        pipe = pipes[name]
+        pipe.process_stats = {"s_encode": 0.0, "raw_bytes": 0, "encoded_bytes": 0}
+        codec.encode = (lambda px, q: pillow_webp(px)) if name == "host_webp" else host_encode
+        try:
+            t0 = time.perf_counter()
+            done, files = 0, None
+            while done < a.images:
+                n = min(a.batch, a.images - done)
+                files, _ = pipe.process([blobs[(done + k) % len(blobs)] for k in range(n)], [options] * n)
+                done += n
+            return done / (time.perf_counter() - t0), dict(pipe.process_stats), files
+        finally:
+            codec.encode = host_encode
+
+    pipes = {"gpu_png": codec.CodecPipeline(ctx, a.threads, gpu_encode=True, gpu_png=True),
+             "gpu_webp": codec.CodecPipeline(ctx, a.threads, gpu_encode=True, gpu_png=True, gpu_webp=True),
+             "host_webp": codec.CodecPipeline(ctx, a.threads)}
+    runs = {k: [] for k in pipes}
+    last = {}
+    for k in pipes:  # warm-up: every shape, every scratch buffer at its size
+        one_pass(k)
+    for _ in range(a.reps):
+        for k in pipes:
+            ips, st, last[k] = one_pass(k)
+            runs[k].append((ips, st))
+    out = {"source": f"{W}x{H} RGBA PNG", "options": options, "batch": a.batch, "threads": a.threads,
+           "images": a.images, "reps": a.reps}
+    nb = (a.images + a.batch - 1) // a.batch
+    for k in pipes:
+        st = runs[k][-1][1]
+        out[k] = {"images_per_s": spread([r[0] for r in runs[k]]),
+                  "s_encode": spread([r[1]["s_encode"] for r in runs[k]]),
+                  "raw_bytes_per_batch": st["raw_bytes"] // nb, "file_bytes_per_batch": st["encoded_bytes"] // nb}
+    n8 = min(8, len(last["gpu_webp"]))
+    pixels = [codec.decode(f) for f in last["gpu_png"][:n8]]
+    for g, hw, p in zip(last["gpu_webp"][:n8], last["host_webp"][:n8], pixels):
+        assert g[:4] == b"RIFF" and np.array_equal(np.asarray(Image.open(io.BytesIO(g))), p)
+        vis = p[..., 3] > 0  # (libwebp without exact=True rewrites the colour under alpha 0)
+        assert np.array_equal(np.asarray(Image.open(io.BytesIO(hw)))[vis], p[vis])
+    tot = {"gpu_webp": sum(len(f) for f in last["gpu_webp"][:n8]), "gpu_png": sum(len(f) for f in last["gpu_png"][:n8])}
+    for m in (0, 4, 6):
+        tot[f"libwebp_method{m}"] = sum(len(pillow_webp(p, m)) for p in pixels)
+    out["sizes"] = {"bytes": tot, **{f"gpu_webp_vs_{k}": round(tot["gpu_webp"] / v, 4)
+                                      for k, v in tot.items() if k != "gpu_webp"}}
+    ctx.set_timing(1)
+    ctx.reset_stats()
+    one_pass("gpu_webp")
+    out["kernel_ms_per_pass"] = {}
+    for name in ("k_webp_pred", "k_webp_lz", "k_webp_codes", "k_webp_emit", "k_webp_pack"):
+        ms, launches, _ = ctx.stats(name)
+        out["kernel_ms_per_pass"][name] = {"ms": round(ms, 3), "launches": launches}
+    ctx.set_timing(0)
+    ctx.reset_stats()
+    for p in pipes.values():
+        p.close()
+    ctx.close()
+    print(json.dumps({"gpu_webp_ab": out}))
 
 
 def png_decode_ab(a):
