@@ -1,5 +1,7 @@
-// fi_jpeg_api.cpp -- the GPU JPEG decode / encode and PNG encode / decode entry points of the runtime
-// (fi_runtime.h; the codecs are fi_jpeg.hip, fi_jpeg_enc.hip, fi_png_enc.hip, fi_png_dec.hip and their host halves).
+// fi_jpeg_api.cpp -- the GPU codec entry points of the runtime (fi_runtime.h): JPEG decode, baseline and
+// progressive JPEG encode, PNG encode and decode, lossless WebP encode.  The codecs are fi_jpeg.hip, fi_jpeg_enc.hip,
+// fi_jpeg_penc.hip, fi_png_enc.hip, fi_webp_enc.hip, fi_png_dec.hip and their host halves; what every device entry
+// point does around its batch (device, lock, order, timers, the first failing image) is codec_call, once.
 #include "fi_runtime.h"
 #include "fi_jpeg.h"
 #include "fi_jpeg_enc.h"
@@ -8,6 +10,42 @@
 #include "fi_png_dec.h"
 
 using namespace fi;
+
+// The `alloc` of the codec batches (see jpeg_encode_batch) on the context's
+// buffers: the encoders' set (ENC) or the decoders'.
+template <bool ENC>
+static void *codec_alloc(void *actx, int which, size_t bytes) {
+  fi_ctx *c = static_cast<fi_ctx *>(actx);
+  if (which == 3) {  // pinned host staging (no copy of an earlier request is in flight: the batches synchronise)
+    void **host = ENC ? &c->jpeg_enc_host : &c->jpeg_host;
+    return ensure_pinned_buf(host, ENC ? &c->jpeg_enc_host_cap : &c->jpeg_host_cap, bytes) == FI_OK ? *host : nullptr;
+  }
+  DevBuf *b = &(ENC ? c->jpeg_enc : c->jpeg)[which];
+  return ensure(c, b, bytes) == FI_OK ? b->p : nullptr;
+}
+static void codec_stage(void *actx, const char *name) {  // ends the running kernel's range, starts `name`'s
+  fi_ctx *c = static_cast<fi_ctx *>(actx);
+  delete c->jpeg_enc_timer;
+  c->jpeg_enc_timer = name ? new Timer(c, name, 0) : nullptr;
+}
+// One codec batch of n > 0 images on the context's stream, under its lock and
+// behind fi_apply: `run(&err)` is the batch (its kernels timed through
+// codec_stage); then the first image it turned down, if any, is the call's
+// error, with `what(status)` as its message.
+template <typename Run, typename What>
+static int codec_call(fi_ctx *c, int32_t n, const int32_t *status, Run run, What what) {
+  HIP_TRY(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
+  std::string err;
+  const int rc = run(&err);
+  codec_stage(c, nullptr);
+  collect_timers(c);
+  if (rc) return set_err(rc, "%s", err.c_str());
+  for (int i = 0; i < n; i++)  // the others are done
+    if (status[i]) return set_err(status[i], "image %d: %s", i, what(status[i]));
+  return FI_OK;
+}
 
 extern "C" {
 
@@ -29,13 +67,6 @@ int fi_jpeg_info_ex(const uint8_t *data, size_t len, uint32_t flags, int32_t *w,
 int fi_jpeg_info(const uint8_t *data, size_t len, int32_t *w, int32_t *h, int32_t *channels) {
   return fi_jpeg_info_ex(data, len, 0, w, h, channels, nullptr, nullptr);
 }
-static void *jpeg_alloc(void *actx, int which, size_t bytes) {
-  fi_ctx *c = static_cast<fi_ctx *>(actx);
-  if (which == 3)  // pinned host staging (the previous call has synchronised)
-    return ensure_pinned_buf(&c->jpeg_host, &c->jpeg_host_cap, bytes) == FI_OK ? c->jpeg_host : nullptr;
-  return ensure(c, &c->jpeg[which], bytes) == FI_OK ? c->jpeg[which].p : nullptr;
-}
-static void jpeg_enc_stage(void *actx, const char *name);
 int fi_jpeg_orientation(const uint8_t *data, size_t len, int32_t *orientation) {
   if (!data || !orientation) return set_err(FI_EINVAL, "bad arguments");
   int o = 1;
@@ -52,22 +83,16 @@ int fi_jpeg_decode_device_view(fi_ctx *c, const uint8_t *const *data, const size
       (out_channels != 0 && out_channels != 3) || (flags & ~FI_JPEG_PROGRESSIVE))
     return set_err(FI_EINVAL, "bad arguments");
   if (n == 0) return FI_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
-  std::string err;
-  // (the stage callback times k_jpeg_prog and the colour kernels the way the encode kernels are timed)
-  const int rc = jpeg_decode_batch(c->stream, data, len, n, dst, dst_stride, out_channels, flags, views, status,
-                                   jpeg_alloc, jpeg_enc_stage, c, &err);
-  jpeg_enc_stage(c, nullptr);
-  collect_timers(c);
-  if (rc) return set_err(rc, "%s", err.c_str());
-  for (int i = 0; i < n; i++)  // the others are decoded; the caller decodes these on the host
-    if (status[i])
-      return set_err(status[i], "image %d: %s", i,
-                     status[i] == FI_EUNSUPPORTED ? "JPEG stream or EXIF orientation the GPU decoder does not handle"
-                                                  : "malformed JPEG or bad view");
-  return FI_OK;
+  return codec_call(
+      c, n, status,
+      [&](std::string *err) {
+        return jpeg_decode_batch(c->stream, data, len, n, dst, dst_stride, out_channels, flags, views, status,
+                                 codec_alloc<false>, codec_stage, c, err);
+      },
+      [](int s) {  // the caller decodes these on the host
+        return s == FI_EUNSUPPORTED ? "JPEG stream or EXIF orientation the GPU decoder does not handle"
+                                    : "malformed JPEG or bad view";
+      });
 }
 int fi_jpeg_decode_device_ex(fi_ctx *c, const uint8_t *const *data, const size_t *len, int32_t n, uint8_t *const *dst,
                              const int64_t *dst_stride, int32_t out_channels, uint32_t flags, int32_t *status) {
@@ -111,17 +136,6 @@ int fi_jpeg_encode_bound(int32_t w, int32_t h, int32_t channels, int32_t quality
                                              : "bad JPEG dimensions or quality");
   return FI_OK;
 }
-static void *jpeg_enc_alloc(void *actx, int which, size_t bytes) {
-  fi_ctx *c = static_cast<fi_ctx *>(actx);
-  if (which == 3)  // pinned host staging (no copy of an earlier request is in flight: see jpeg_encode_batch)
-    return ensure_pinned_buf(&c->jpeg_enc_host, &c->jpeg_enc_host_cap, bytes) == FI_OK ? c->jpeg_enc_host : nullptr;
-  return ensure(c, &c->jpeg_enc[which], bytes) == FI_OK ? c->jpeg_enc[which].p : nullptr;
-}
-static void jpeg_enc_stage(void *actx, const char *name) {  // ends the running kernel's range, starts `name`'s
-  fi_ctx *c = static_cast<fi_ctx *>(actx);
-  delete c->jpeg_enc_timer;
-  c->jpeg_enc_timer = name ? new Timer(c, name, 0) : nullptr;
-}
 int fi_jpeg_encode_bound_ex(int32_t w, int32_t h, int32_t channels, int32_t quality, int32_t subsampling,
                             uint32_t flags, size_t *bytes) {
   if (!bytes || (flags & ~FI_JPEG_ENC_PROGRESSIVE)) return set_err(FI_EINVAL, "bad arguments");
@@ -163,23 +177,18 @@ int fi_jpeg_encode_device_ex(fi_ctx *c, const uint8_t *const *src, const int32_t
                  !out_len || !status)))
     return set_err(FI_EINVAL, "bad arguments");
   if (n == 0) return FI_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
-  std::string err;
-  const int rc = (flags & FI_JPEG_ENC_PROGRESSIVE ? jpeg_pencode_batch : jpeg_encode_batch)(
-      c->stream, src, w, h, channels, src_stride, quality, subsampling, n, out, out_cap, out_len, status,
-      jpeg_enc_alloc, jpeg_enc_stage, c, &err);
-  jpeg_enc_stage(c, nullptr);
-  collect_timers(c);
-  if (rc) return set_err(rc, "%s", err.c_str());
-  for (int i = 0; i < n; i++)  // the others are encoded
-    if (status[i])
-      return set_err(status[i], "image %d: %s", i,
-                     status[i] == FI_EUNSUPPORTED ? "channel count or subsampling the GPU JPEG encoder does not write"
-                     : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
-                                                  : "bad JPEG source, dimensions or quality");
-  return FI_OK;
+  return codec_call(
+      c, n, status,
+      [&](std::string *err) {
+        return (flags & FI_JPEG_ENC_PROGRESSIVE ? jpeg_pencode_batch : jpeg_encode_batch)(
+            c->stream, src, w, h, channels, src_stride, quality, subsampling, n, out, out_cap, out_len, status,
+            codec_alloc<true>, codec_stage, c, err);
+      },
+      [](int s) {
+        return s == FI_EUNSUPPORTED ? "channel count or subsampling the GPU JPEG encoder does not write"
+               : s == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
+                                    : "bad JPEG source, dimensions or quality";
+      });
 }
 // GPU PNG encode (fi_png_enc.hip): the outputs JPEG cannot carry (alpha); the
 // JPEG encoder's scratch, staging and timing plumbing
@@ -196,22 +205,17 @@ int fi_png_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w,
   if (!c || n < 0 || (n > 0 && (!src || !w || !h || !channels || !src_stride || !out || !out_cap || !out_len || !status)))
     return set_err(FI_EINVAL, "bad arguments");
   if (n == 0) return FI_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
-  std::string err;
-  const int rc = png_encode_batch(c->stream, src, w, h, channels, src_stride, filter, n, out, out_cap, out_len, status,
-                                  jpeg_enc_alloc, jpeg_enc_stage, c, &err);
-  jpeg_enc_stage(c, nullptr);
-  collect_timers(c);
-  if (rc) return set_err(rc, "%s", err.c_str());
-  for (int i = 0; i < n; i++)  // the others are encoded
-    if (status[i])
-      return set_err(status[i], "image %d: %s", i,
-                     status[i] == FI_EUNSUPPORTED ? "filtered stream beyond 2^31 - 1 bytes"
-                     : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
-                                                  : "bad PNG source, dimensions, channels or filter");
-  return FI_OK;
+  return codec_call(
+      c, n, status,
+      [&](std::string *err) {
+        return png_encode_batch(c->stream, src, w, h, channels, src_stride, filter, n, out, out_cap, out_len, status,
+                                codec_alloc<true>, codec_stage, c, err);
+      },
+      [](int s) {
+        return s == FI_EUNSUPPORTED ? "filtered stream beyond 2^31 - 1 bytes"
+               : s == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
+                                    : "bad PNG source, dimensions, channels or filter";
+      });
 }
 // GPU lossless WebP encode (fi_webp_enc.hip): the PNG encoder's conventions and plumbing
 int fi_webp_encode_bound(int32_t w, int32_t h, int32_t channels, size_t *bytes) {
@@ -236,22 +240,17 @@ int fi_webp_encode_device(fi_ctx *c, const uint8_t *const *src, const int32_t *w
   if (!c || n < 0 || (n > 0 && (!src || !w || !h || !channels || !src_stride || !out || !out_cap || !out_len || !status)))
     return set_err(FI_EINVAL, "bad arguments");
   if (n == 0) return FI_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
-  std::string err;
-  const int rc = webp_encode_batch(c->stream, src, w, h, channels, src_stride, predictor, n, out, out_cap, out_len,
-                                   status, jpeg_enc_alloc, jpeg_enc_stage, c, &err);
-  jpeg_enc_stage(c, nullptr);
-  collect_timers(c);
-  if (rc) return set_err(rc, "%s", err.c_str());
-  for (int i = 0; i < n; i++)  // the others are encoded
-    if (status[i])
-      return set_err(status[i], "image %d: %s", i,
-                     status[i] == FI_EUNSUPPORTED ? "a side above 16384"
-                     : status[i] == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
-                                                  : "bad WebP source, dimensions, channels or predictor");
-  return FI_OK;
+  return codec_call(
+      c, n, status,
+      [&](std::string *err) {
+        return webp_encode_batch(c->stream, src, w, h, channels, src_stride, predictor, n, out, out_cap, out_len,
+                                 status, codec_alloc<true>, codec_stage, c, err);
+      },
+      [](int s) {
+        return s == FI_EUNSUPPORTED ? "a side above 16384"
+               : s == FI_ENOMEM     ? "out_cap is below the encoded size (out_len)"
+                                    : "bad WebP source, dimensions, channels or predictor";
+      });
 }
 // GPU PNG decode (fi_png_dec.hip): the sources a JPEG cannot be (alpha, palette); the JPEG
 // decoder's scratch, staging and timing plumbing
@@ -273,21 +272,16 @@ int fi_png_decode_device(fi_ctx *c, const uint8_t *const *data, const size_t *le
   if (!c || n < 0 || (n > 0 && (!data || !len || !dst || !dst_stride || !status)))
     return set_err(FI_EINVAL, "bad arguments");
   if (n == 0) return FI_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (order_after_apply(c) != FI_OK) return set_err(FI_EDEVICE, "hipStreamWaitEvent failed");
-  std::string err;
-  const int rc = png_decode_batch(c->stream, data, len, n, dst, dst_stride, out_channels, status, jpeg_alloc,
-                                  jpeg_enc_stage, c, &err);
-  jpeg_enc_stage(c, nullptr);
-  collect_timers(c);
-  if (rc) return set_err(rc, "%s", err.c_str());
-  for (int i = 0; i < n; i++)  // the others are decoded; the caller decodes these on the host
-    if (status[i])
-      return set_err(status[i], "image %d: %s", i,
-                     status[i] == FI_EUNSUPPORTED ? "PNG file the GPU decoder does not handle"
-                                                  : "malformed PNG, or out_channels / dst_stride that do not fit it");
-  return FI_OK;
+  return codec_call(
+      c, n, status,
+      [&](std::string *err) {
+        return png_decode_batch(c->stream, data, len, n, dst, dst_stride, out_channels, status, codec_alloc<false>,
+                                codec_stage, c, err);
+      },
+      [](int s) {  // the caller decodes these on the host
+        return s == FI_EUNSUPPORTED ? "PNG file the GPU decoder does not handle"
+                                    : "malformed PNG, or out_channels / dst_stride that do not fit it";
+      });
 }
 
 }  // extern "C"

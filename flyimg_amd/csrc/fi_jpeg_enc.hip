@@ -27,10 +27,11 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 #include <vector>
 
+#include "fi_enc_batch.h"
+#include "fi_enc_pack.h"
 #include "fi_internal.h"
 #include "fi_jpeg_enc.h"
 #include "fi_jpeg_enc_dev.h"
@@ -412,41 +413,14 @@ __global__ __launch_bounds__(256) void k_jpeg_scan(const JpegEncDesc *__restrict
                                                    const JpegEncIv *__restrict__ ivs, int niv,
                                                    const int32_t *__restrict__ ivlen, int64_t *__restrict__ ivdst,
                                                    int64_t *__restrict__ imgpos) {
-  __shared__ int64_t part[256];
-  __shared__ int64_t base;
-  const int t = threadIdx.x;
-  if (t == 0) base = 0;
-  __syncthreads();
-  for (int i0 = 0; i0 < niv; i0 += 256) {
-    const int iv = i0 + t;
-    int64_t v = 0;
-    bool first = false, lastiv = false;
-    int img = 0;
-    if (iv < niv) {
-      const JpegEncIv I = ivs[iv];
-      img = I.img;
-      first = I.row == 0;
-      lastiv = I.row == descs[img].mcuy - 1;
-      v = ivlen[iv] + (first ? descs[img].hdr_len : 0) + (lastiv ? 2 : 0);
-    }
-    part[t] = v;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-      const int64_t a = t >= d ? part[t - d] : 0;
-      __syncthreads();
-      part[t] += a;
-      __syncthreads();
-    }
-    const int64_t start = base + part[t] - v;
-    if (iv < niv) {
-      ivdst[iv] = start;
-      if (first) imgpos[2 * img] = start;
-    }
-    __syncthreads();
-    if (iv < niv && lastiv) imgpos[2 * img + 1] = start + v;
-    if (t == 255) base += part[255];
-    __syncthreads();
-  }
+  enc_scan_items(
+      niv,
+      [=](int iv) {
+        const JpegEncIv I = ivs[iv];
+        const bool first = I.row == 0, last = I.row == descs[I.img].mcuy - 1;
+        return EncItem{ivlen[iv] + (first ? descs[I.img].hdr_len : 0) + (last ? 2 : 0), I.img, first, last};
+      },
+      ivdst, imgpos);
 }
 
 // one workgroup per interval: header (first interval), slot, EOI (last) -> packed
@@ -467,18 +441,7 @@ __global__ __launch_bounds__(256) void k_jpeg_pack(const JpegEncDesc *__restrict
   }
   const uint8_t *s = slots + D.slot0 + (int64_t)I.row * D.slot_bytes;
   const int n = ivlen[iv];
-  // dword stores once dst is aligned (the slot's bytes come through the cache)
-  const int head = jpeg_imin(n, (int)((4 - (reinterpret_cast<uintptr_t>(dst) & 3)) & 3));
-  if (t < head) dst[t] = s[t];
-  const int nw = (n - head) >> 2;
-  uint32_t *dw = reinterpret_cast<uint32_t *>(dst + head);
-  const uint8_t *sw = s + head;
-  for (int i = t; i < nw; i += 256) {
-    const uint8_t *p = sw + 4 * i;
-    dw[i] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-  }
-  const int tail0 = head + 4 * nw;
-  if (t < n - tail0) dst[tail0 + t] = s[tail0 + t];
+  enc_copy_aligned(dst, s, n, t, 256);
   if (I.row == D.mcuy - 1 && t == 0) {  // EOI
     dst[n] = 0xFF;
     dst[n + 1] = 0xD9;
@@ -502,34 +465,18 @@ int jpeg_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
   std::vector<JpegEncDesc> descs;
   std::vector<int> desc_img;
   std::vector<JpegEncIv> ivs;
-  std::vector<uint16_t> qts;
-  std::map<int, int> qt_ix;  // quality -> table pair
+  JpegEncQts qts;
   std::vector<uint8_t> hdrs;
   int64_t nblocks = 0;
   size_t slot_total = 0, bound_total = 0;
   for (int i = 0; i < n; i++) {
     out_len[i] = 0;
-    status[i] = jpeg_enc_check(w[i], h[i], channels[i], quality[i], subsampling[i]);
-    if (!status[i] && (!src[i] || src_stride[i] < (int64_t)w[i] * channels[i] || (out_cap[i] && !out[i])))
-      status[i] = FI_EINVAL;
+    status[i] = enc_io_status(jpeg_enc_check(w[i], h[i], channels[i], quality[i], subsampling[i]), src[i],
+                              src_stride[i], w[i], channels[i], out[i], out_cap[i]);
     if (status[i]) continue;
-    JpegEncDesc D{};
-    D.src = src[i];
-    D.stride = src_stride[i];
-    D.W = w[i];
-    D.H = h[i];
-    D.C = channels[i];
-    jpeg_enc_grid(D.W, D.H, D.C, subsampling[i], &D.bpm, &D.mcux, &D.mcuy);
-    auto it = qt_ix.find(quality[i]);
-    if (it == qt_ix.end()) {
-      uint16_t t[2][64];
-      jpeg_enc_quant_tables(quality[i], t);
-      it = qt_ix.emplace(quality[i], (int)(qts.size() / 128)).first;
-      qts.insert(qts.end(), &t[0][0], &t[0][0] + 128);
-    }
-    D.qt = it->second;
+    JpegEncDesc D =
+        jpeg_enc_desc(src[i], src_stride[i], w[i], h[i], channels[i], quality[i], subsampling[i], nblocks, &qts);
     D.iv0 = (int)ivs.size();
-    D.blk0 = nblocks;
     D.slot0 = (int64_t)slot_total;
     D.slot_bytes = (int64_t)((jpeg_enc_slot_bytes(D.bpm, D.mcux) + 15) & ~(size_t)15);
     D.hdr_off = (int32_t)hdrs.size();
@@ -550,22 +497,24 @@ int jpeg_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
   }
   if (descs.empty()) return 0;
   const int nd = (int)descs.size(), niv = (int)ivs.size();
-  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
   // upload: descriptors, intervals, quantisation tables, Huffman tables, headers
   uint32_t huff[1024];
   jpeg_enc_huff_tables(huff);
-  const size_t o_desc = 0, o_iv = o_desc + up256(descs.size() * sizeof(JpegEncDesc));
-  const size_t o_qt = o_iv + up256(ivs.size() * sizeof(JpegEncIv));
-  const size_t o_huff = o_qt + up256(qts.size() * 2);
-  const size_t o_hdr = o_huff + up256(sizeof(huff));
-  const size_t up_total = o_hdr + up256(hdrs.size());
+  EncArena up, work;
+  const size_t o_desc = up.add(descs.size() * sizeof(JpegEncDesc));
+  const size_t o_iv = up.add(ivs.size() * sizeof(JpegEncIv));
+  const size_t o_qt = up.add(qts.tabs.size() * 2);
+  const size_t o_huff = up.add(sizeof(huff));
+  const size_t o_hdr = up.add(hdrs.size());
+  const size_t up_total = up.total();
   // work: coefficients, AC bit counts, interval lengths / destinations, image positions, slots
-  const size_t k_coef = 0, k_bits = k_coef + up256((size_t)nblocks * 128);
-  const size_t k_ivlen = k_bits + up256((size_t)nblocks * 2);
-  const size_t k_ivdst = k_ivlen + up256((size_t)niv * 4);
-  const size_t k_pos = k_ivdst + up256((size_t)niv * 8);
-  const size_t k_slots = k_pos + up256((size_t)nd * 16);
-  const size_t work_total = k_slots + slot_total;
+  const size_t k_coef = work.add((size_t)nblocks * 128);
+  const size_t k_bits = work.add((size_t)nblocks * 2);
+  const size_t k_ivlen = work.add((size_t)niv * 4);
+  const size_t k_ivdst = work.add((size_t)niv * 8);
+  const size_t k_pos = work.add((size_t)nd * 16);
+  const size_t k_slots = work.add(slot_total);
+  const size_t work_total = work.total();
   uint8_t *dup = (uint8_t *)alloc(actx, 0, up_total);
   uint8_t *hst = (uint8_t *)alloc(actx, 3, std::max(up_total, (size_t)nd * 16));
   uint8_t *dwork = (uint8_t *)alloc(actx, 1, work_total);
@@ -576,7 +525,7 @@ int jpeg_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
   }
   memcpy(hst + o_desc, descs.data(), descs.size() * sizeof(JpegEncDesc));
   memcpy(hst + o_iv, ivs.data(), ivs.size() * sizeof(JpegEncIv));
-  memcpy(hst + o_qt, qts.data(), qts.size() * 2);
+  memcpy(hst + o_qt, qts.tabs.data(), qts.tabs.size() * 2);
   memcpy(hst + o_huff, huff, sizeof(huff));
   memcpy(hst + o_hdr, hdrs.data(), hdrs.size());
   if (hipMemcpyAsync(dup, hst, up_total, hipMemcpyHostToDevice, st) != hipSuccess) {
@@ -601,41 +550,7 @@ int jpeg_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
   hipLaunchKernelGGL(k_jpeg_pack, dim3((unsigned)niv), dim3(256), 0, st, dd, div, niv, divlen, divdst, dup + o_hdr,
                      dwork + k_slots, dpack);
   stage(actx, nullptr);
-  // the image positions, then exactly the packed bytes
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(hst, dpos, (size_t)nd * 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    *err = "JPEG encode kernels";
-    return FI_EDEVICE;
-  }
-  std::vector<int64_t> pos((size_t)nd * 2);
-  memcpy(pos.data(), hst, (size_t)nd * 16);
-  const int64_t total = pos[2 * (size_t)nd - 1];
-  if (total < 0 || (size_t)total > bound_total) {
-    *err = "JPEG encode: packed size out of range";
-    return FI_EDEVICE;
-  }
-  hst = (uint8_t *)alloc(actx, 3, (size_t)total);
-  if (!hst) {
-    *err = "pinned memory for the JPEG encode download";
-    return FI_ENOMEM;
-  }
-  if (hipMemcpyAsync(hst, dpack, (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    *err = "JPEG encode download";
-    return FI_EDEVICE;
-  }
-  for (int k = 0; k < nd; k++) {
-    const int i = desc_img[k];
-    const size_t len = (size_t)(pos[2 * k + 1] - pos[2 * k]);
-    out_len[i] = len;
-    if (len > out_cap[i]) {
-      status[i] = FI_ENOMEM;  // the caller's buffer is too small: nothing is written past it
-      if (out_cap[i]) memcpy(out[i], hst + pos[2 * k], out_cap[i]);
-      continue;
-    }
-    memcpy(out[i], hst + pos[2 * k], len);
-  }
-  return 0;
+  return enc_finish(st, alloc, actx, hst, dpos, nd, nullptr, dpack, bound_total, "JPEG", desc_img, out, out_cap, out_len,
+                    status, true, err);
 }
 }  // namespace fi

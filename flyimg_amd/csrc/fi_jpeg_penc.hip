@@ -26,10 +26,11 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 #include <vector>
 
+#include "fi_enc_batch.h"
+#include "fi_enc_pack.h"
 #include "fi_internal.h"
 #include "fi_jpeg_enc.h"
 #include "fi_jpeg_enc_dev.h"
@@ -181,37 +182,13 @@ __global__ __launch_bounds__(256) void k_jpeg_pscan(const PencPiece *__restrict_
                                                     const int32_t *__restrict__ dhtlen,
                                                     const int32_t *__restrict__ ivlen, int64_t *__restrict__ dst,
                                                     int64_t *__restrict__ imgpos) {
-  __shared__ int64_t part[256];
-  __shared__ int64_t base;
-  const int t = threadIdx.x;
-  if (t == 0) base = 0;
-  __syncthreads();
-  for (int i0 = 0; i0 < np; i0 += 256) {
-    const int p = i0 + t;
-    int64_t v = 0;
-    PencPiece P{};
-    if (p < np) {
-      P = pieces[p];
-      v = penc_piece_len(P, dhtlen, ivlen);
-    }
-    part[t] = v;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-      const int64_t a = t >= d ? part[t - d] : 0;
-      __syncthreads();
-      part[t] += a;
-      __syncthreads();
-    }
-    const int64_t start = base + part[t] - v;
-    if (p < np) {
-      dst[p] = start;
-      if (P.first) imgpos[2 * P.img] = start;
-      if (P.last) imgpos[2 * P.img + 1] = start + v;
-    }
-    __syncthreads();
-    if (t == 255) base += part[255];
-    __syncthreads();
-  }
+  enc_scan_items(
+      np,
+      [=](int p) {
+        const PencPiece P = pieces[p];
+        return EncItem{penc_piece_len(P, dhtlen, ivlen), P.img, P.first != 0, P.last != 0};
+      },
+      dst, imgpos);
 }
 
 __global__ __launch_bounds__(64) void k_jpeg_ppack(const PencPiece *__restrict__ pieces, int np,
@@ -241,34 +218,18 @@ int jpeg_pencode_batch(hipStream_t st, const uint8_t *const *src, const int32_t 
   std::vector<int> desc_img;
   std::vector<PencGrp> grps;
   std::vector<PencPiece> pieces;
-  std::vector<uint16_t> qts;
-  std::map<int, int> qt_ix;  // quality -> table pair
+  JpegEncQts qts;
   std::vector<uint8_t> segs;  // the bytes the host knows: heads, DRI / SOS, EOI
   int64_t nblocks = 0, niv = 0;
   size_t slot_total = 0, bound_total = 0;
   for (int i = 0; i < n; i++) {
     out_len[i] = 0;
-    status[i] = jpeg_enc_check(w[i], h[i], channels[i], quality[i], subsampling[i]);
-    if (!status[i] && (!src[i] || src_stride[i] < (int64_t)w[i] * channels[i] || (out_cap[i] && !out[i])))
-      status[i] = FI_EINVAL;
+    status[i] = enc_io_status(jpeg_enc_check(w[i], h[i], channels[i], quality[i], subsampling[i]), src[i],
+                              src_stride[i], w[i], channels[i], out[i], out_cap[i]);
     if (status[i]) continue;
     const int img = (int)descs.size();
-    JpegEncDesc D{};
-    D.src = src[i];
-    D.stride = src_stride[i];
-    D.W = w[i];
-    D.H = h[i];
-    D.C = channels[i];
-    jpeg_enc_grid(D.W, D.H, D.C, subsampling[i], &D.bpm, &D.mcux, &D.mcuy);
-    auto it = qt_ix.find(quality[i]);
-    if (it == qt_ix.end()) {
-      uint16_t t[2][64];
-      jpeg_enc_quant_tables(quality[i], t);
-      it = qt_ix.emplace(quality[i], (int)(qts.size() / 128)).first;
-      qts.insert(qts.end(), &t[0][0], &t[0][0] + 128);
-    }
-    D.qt = it->second;
-    D.blk0 = nblocks;
+    const JpegEncDesc D =
+        jpeg_enc_desc(src[i], src_stride[i], w[i], h[i], channels[i], quality[i], subsampling[i], nblocks, &qts);
     PencImg I{};
     penc_geom(D.W, D.H, D.C, subsampling[i], &I.G);
     I.blk0 = nblocks;
@@ -317,29 +278,31 @@ int jpeg_pencode_batch(hipStream_t st, const uint8_t *const *src, const int32_t 
   if (descs.empty()) return 0;
   const int nd = (int)descs.size(), ngrp = (int)grps.size(), np = (int)pieces.size();
   const int ntab = nd * kPencTabs;
-  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
   // upload: descriptors, images, groups, pieces, quantisation tables, the Annex K tables (k_jpeg_fdct), segments
   uint32_t huff[1024];
   jpeg_enc_huff_tables(huff);
-  const size_t o_desc = 0, o_img = o_desc + up256(descs.size() * sizeof(JpegEncDesc));
-  const size_t o_grp = o_img + up256(imgs.size() * sizeof(PencImg));
-  const size_t o_piece = o_grp + up256(grps.size() * sizeof(PencGrp));
-  const size_t o_qt = o_piece + up256(pieces.size() * sizeof(PencPiece));
-  const size_t o_huff = o_qt + up256(qts.size() * 2);
-  const size_t o_seg = o_huff + up256(sizeof(huff));
-  const size_t up_total = o_seg + up256(segs.size());
+  EncArena up, work;
+  const size_t o_desc = up.add(descs.size() * sizeof(JpegEncDesc));
+  const size_t o_img = up.add(imgs.size() * sizeof(PencImg));
+  const size_t o_grp = up.add(grps.size() * sizeof(PencGrp));
+  const size_t o_piece = up.add(pieces.size() * sizeof(PencPiece));
+  const size_t o_qt = up.add(qts.tabs.size() * 2);
+  const size_t o_huff = up.add(sizeof(huff));
+  const size_t o_seg = up.add(segs.size());
+  const size_t up_total = up.total();
   // work: coefficients, AC bit counts (unused here), histograms, codes, DHT bytes and lengths, interval lengths,
   // piece destinations, image positions, slots
-  const size_t k_coef = 0, k_bits = k_coef + up256((size_t)nblocks * 128);
-  const size_t k_hist = k_bits + up256((size_t)nblocks * 2);
-  const size_t k_code = k_hist + up256((size_t)ntab * kPencHist * 4);
-  const size_t k_dht = k_code + up256((size_t)ntab * 256 * 4);
-  const size_t k_dhtlen = k_dht + up256((size_t)ntab * kPencDhtPitch);
-  const size_t k_ivlen = k_dhtlen + up256((size_t)ntab * 4);
-  const size_t k_dst = k_ivlen + up256((size_t)niv * 4);
-  const size_t k_pos = k_dst + up256((size_t)np * 8);
-  const size_t k_slots = k_pos + up256((size_t)nd * 16);
-  const size_t work_total = k_slots + slot_total;
+  const size_t k_coef = work.add((size_t)nblocks * 128);
+  const size_t k_bits = work.add((size_t)nblocks * 2);
+  const size_t k_hist = work.add((size_t)ntab * kPencHist * 4);
+  const size_t k_code = work.add((size_t)ntab * 256 * 4);
+  const size_t k_dht = work.add((size_t)ntab * kPencDhtPitch);
+  const size_t k_dhtlen = work.add((size_t)ntab * 4);
+  const size_t k_ivlen = work.add((size_t)niv * 4);
+  const size_t k_dst = work.add((size_t)np * 8);
+  const size_t k_pos = work.add((size_t)nd * 16);
+  const size_t k_slots = work.add(slot_total);
+  const size_t work_total = work.total();
   uint8_t *dup = (uint8_t *)alloc(actx, 0, up_total);
   uint8_t *hst = (uint8_t *)alloc(actx, 3, std::max(up_total, (size_t)nd * 16));
   uint8_t *dwork = (uint8_t *)alloc(actx, 1, work_total);
@@ -352,7 +315,7 @@ int jpeg_pencode_batch(hipStream_t st, const uint8_t *const *src, const int32_t 
   memcpy(hst + o_img, imgs.data(), imgs.size() * sizeof(PencImg));
   memcpy(hst + o_grp, grps.data(), grps.size() * sizeof(PencGrp));
   memcpy(hst + o_piece, pieces.data(), pieces.size() * sizeof(PencPiece));
-  memcpy(hst + o_qt, qts.data(), qts.size() * 2);
+  memcpy(hst + o_qt, qts.tabs.data(), qts.tabs.size() * 2);
   memcpy(hst + o_huff, huff, sizeof(huff));
   memcpy(hst + o_seg, segs.data(), segs.size());
   if (hipMemcpyAsync(dup, hst, up_total, hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -388,41 +351,7 @@ int jpeg_pencode_batch(hipStream_t st, const uint8_t *const *src, const int32_t 
   hipLaunchKernelGGL(k_jpeg_ppack, dim3((unsigned)np), dim3(64), 0, st, dpiece, np, ddhtlen, divlen, ddst,
                      dup + o_seg, ddht, dwork + k_slots, dpack);
   stage(actx, nullptr);
-  // the image positions, then exactly the packed bytes
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(hst, dpos, (size_t)nd * 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    *err = "JPEG encode kernels";
-    return FI_EDEVICE;
-  }
-  std::vector<int64_t> pos((size_t)nd * 2);
-  memcpy(pos.data(), hst, (size_t)nd * 16);
-  const int64_t total = pos[2 * (size_t)nd - 1];
-  if (total < 0 || (size_t)total > bound_total) {
-    *err = "JPEG encode: packed size out of range";
-    return FI_EDEVICE;
-  }
-  hst = (uint8_t *)alloc(actx, 3, (size_t)total);
-  if (!hst) {
-    *err = "pinned memory for the JPEG encode download";
-    return FI_ENOMEM;
-  }
-  if (hipMemcpyAsync(hst, dpack, (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    *err = "JPEG encode download";
-    return FI_EDEVICE;
-  }
-  for (int k = 0; k < nd; k++) {
-    const int i = desc_img[k];
-    const size_t len = (size_t)(pos[2 * k + 1] - pos[2 * k]);
-    out_len[i] = len;
-    if (len > out_cap[i]) {
-      status[i] = FI_ENOMEM;  // the caller's buffer is too small: nothing is written past it
-      if (out_cap[i]) memcpy(out[i], hst + pos[2 * k], out_cap[i]);
-      continue;
-    }
-    memcpy(out[i], hst + pos[2 * k], len);
-  }
-  return 0;
+  return enc_finish(st, alloc, actx, hst, dpos, nd, nullptr, dpack, bound_total, "JPEG", desc_img, out, out_cap, out_len,
+                    status, true, err);
 }
 }  // namespace fi

@@ -30,8 +30,8 @@
 //            IEND) -> the band's slot;
 //   k_png_scan + k_png_pack   exclusive scan of the slot lengths over the batch,
 //            a workgroup per band copies its slot into one contiguous stream,
-//            which the host fetches with one copy (k_jpeg_scan / k_jpeg_pack's
-//            shape without their header / EOI cases).
+//            which the host fetches with one copy (the scan and the copy of
+//            fi_enc_pack.h with a band as the item).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -40,6 +40,8 @@
 #include <string>
 #include <vector>
 
+#include "fi_enc_batch.h"
+#include "fi_enc_pack.h"
 #include "fi_internal.h"
 #include "fi_png_enc.h"
 
@@ -500,55 +502,22 @@ __global__ __launch_bounds__(256) void k_png_scan(const PngDesc *__restrict__ de
                                                   const PngBandRef *__restrict__ bands, int nbands,
                                                   const int32_t *__restrict__ bandlen, int64_t *__restrict__ banddst,
                                                   int64_t *__restrict__ imgpos) {
-  __shared__ int64_t part[256];
-  __shared__ int64_t base;
-  const int t = threadIdx.x;
-  if (t == 0) base = 0;
-  __syncthreads();
-  for (int i0 = 0; i0 < nbands; i0 += 256) {
-    const int b = i0 + t;
-    const int64_t v = b < nbands ? bandlen[b] : 0;
-    part[t] = v;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-      const int64_t a = t >= d ? part[t - d] : 0;
-      __syncthreads();
-      part[t] += a;
-      __syncthreads();
-    }
-    const int64_t start = base + part[t] - v;
-    if (b < nbands) {
-      const PngBandRef B = bands[b];
-      banddst[b] = start;
-      if (B.idx == 0) imgpos[2 * B.img] = start;
-      if (B.idx == descs[B.img].nbands - 1) imgpos[2 * B.img + 1] = start + v;
-    }
-    __syncthreads();
-    if (t == 255) base += part[255];
-    __syncthreads();
-  }
+  enc_scan_items(
+      nbands,
+      [=](int b) {
+        const PngBandRef B = bands[b];
+        return EncItem{bandlen[b], B.img, B.idx == 0, B.idx == descs[B.img].nbands - 1};
+      },
+      banddst, imgpos);
 }
 
 // a workgroup per band: slot -> packed (dword stores once the destination is aligned)
 __global__ __launch_bounds__(256) void k_png_pack(int nbands, const int32_t *__restrict__ bandlen,
                                                   const int64_t *__restrict__ banddst,
                                                   const uint8_t *__restrict__ slots, uint8_t *__restrict__ packed) {
-  const int band = blockIdx.x, t = threadIdx.x;
+  const int band = blockIdx.x;
   if (band >= nbands) return;
-  uint8_t *dst = packed + banddst[band];
-  const uint8_t *s = slots + (int64_t)band * kPngSlotBytes;
-  const int n = bandlen[band];
-  const int head = std::min(n, (int)((4 - (reinterpret_cast<uintptr_t>(dst) & 3)) & 3));
-  if (t < head) dst[t] = s[t];
-  const int nw = (n - head) >> 2;
-  uint32_t *dw = reinterpret_cast<uint32_t *>(dst + head);
-  const uint8_t *sw = s + head;
-  for (int i = t; i < nw; i += 256) {
-    const uint8_t *p = sw + 4 * i;
-    dw[i] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-  }
-  const int tail0 = head + 4 * nw;
-  if (t < n - tail0) dst[tail0 + t] = s[tail0 + t];
+  enc_copy_aligned(packed + banddst[band], slots + (int64_t)band * kPngSlotBytes, bandlen[band], threadIdx.x, 256);
 }
 
 // ---------------------------------------------------------------------------
@@ -568,9 +537,8 @@ int png_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w
   for (int i = 0; i < n; i++) {
     out_len[i] = 0;
     const int f = filter ? filter[i] : -1;
-    status[i] = png_enc_check(w[i], h[i], channels[i], f);
-    if (!status[i] && (!src[i] || src_stride[i] < (int64_t)w[i] * channels[i] || (out_cap[i] && !out[i])))
-      status[i] = FI_EINVAL;
+    status[i] = enc_io_status(png_enc_check(w[i], h[i], channels[i], f), src[i], src_stride[i], w[i], channels[i], out[i],
+                              out_cap[i]);
     if (status[i]) continue;
     PngDesc D{};
     D.src = src[i];
@@ -603,20 +571,23 @@ int png_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w
   if (descs.empty()) return 0;
   const int nd = (int)descs.size(), nb = (int)bands.size();
   // upload: descriptors, bands
-  const size_t o_desc = 0, o_band = o_desc + up256(descs.size() * sizeof(PngDesc));
-  const size_t up_total = o_band + up256(bands.size() * sizeof(PngBandRef));
+  EncArena up, work;
+  const size_t o_desc = up.add(descs.size() * sizeof(PngDesc));
+  const size_t o_band = up.add(bands.size() * sizeof(PngBandRef));
+  const size_t up_total = up.total();
   // work: filtered streams, symbols, symbol counts, histograms, Adler partials, codes, lengths, destinations,
   // image positions, slots
-  const size_t k_stream = 0, k_syms = k_stream + stream_total;
-  const size_t k_nsym = k_syms + stream_total * 4;
-  const size_t k_hist = k_nsym + up256((size_t)nb * 4);
-  const size_t k_adler = k_hist + up256((size_t)nb * kPngHist2 * 4);
-  const size_t k_codes = k_adler + up256((size_t)nb * 8);
-  const size_t k_len = k_codes + up256((size_t)nb * sizeof(PngBandCode));
-  const size_t k_dst = k_len + up256((size_t)nb * 4);
-  const size_t k_pos = k_dst + up256((size_t)nb * 8);
-  const size_t k_slots = k_pos + up256((size_t)nd * 16 + 16);  // (+ the fault word behind the positions)
-  const size_t work_total = k_slots + (size_t)nb * kPngSlotBytes;
+  const size_t k_stream = work.add(stream_total);
+  const size_t k_syms = work.add(stream_total * 4);
+  const size_t k_nsym = work.add((size_t)nb * 4);
+  const size_t k_hist = work.add((size_t)nb * kPngHist2 * 4);
+  const size_t k_adler = work.add((size_t)nb * 8);
+  const size_t k_codes = work.add((size_t)nb * sizeof(PngBandCode));
+  const size_t k_len = work.add((size_t)nb * 4);
+  const size_t k_dst = work.add((size_t)nb * 8);
+  const size_t k_pos = work.add((size_t)nd * 16 + 16);  // (+ the fault word behind the positions)
+  const size_t k_slots = work.add((size_t)nb * kPngSlotBytes);
+  const size_t work_total = work.total();
   uint8_t *dup = (uint8_t *)alloc(actx, 0, up_total);
   uint8_t *hst = (uint8_t *)alloc(actx, 3, std::max(up_total, (size_t)nd * 16 + 16));
   uint8_t *dwork = (uint8_t *)alloc(actx, 1, work_total);
@@ -662,47 +633,8 @@ int png_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *w
   hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(256), 0, st, dd, db, nb, dlen, ddst, dpos);
   hipLaunchKernelGGL(k_png_pack, dim3((unsigned)nb), dim3(256), 0, st, nb, dlen, ddst, dslots, dpack);
   stage(actx, nullptr);
-  // the image positions, then exactly the packed bytes
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(hst, dpos, (size_t)nd * 16 + 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    *err = "PNG encode kernels";
-    return FI_EDEVICE;
-  }
-  std::vector<int64_t> pos((size_t)nd * 2);
-  memcpy(pos.data(), hst, (size_t)nd * 16);
-  int32_t fault = 0;
-  memcpy(&fault, hst + (size_t)nd * 16, 4);
-  if (fault) {
-    *err = "PNG encode: a band's block did not have the size its codes were chosen for";
-    return FI_EDEVICE;
-  }
-  const int64_t total = pos[2 * (size_t)nd - 1];
-  if (total < 0 || (size_t)total > bound_total) {
-    *err = "PNG encode: packed size out of range";
-    return FI_EDEVICE;
-  }
-  hst = (uint8_t *)alloc(actx, 3, (size_t)total);
-  if (!hst) {
-    *err = "pinned memory for the PNG encode download";
-    return FI_ENOMEM;
-  }
-  if (hipMemcpyAsync(hst, dpack, (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    *err = "PNG encode download";
-    return FI_EDEVICE;
-  }
-  for (int k = 0; k < nd; k++) {
-    const int i = desc_img[k];
-    const size_t len = (size_t)(pos[2 * k + 1] - pos[2 * k]);
-    out_len[i] = len;
-    if (len > out_cap[i]) {
-      status[i] = FI_ENOMEM;  // the caller's buffer is too small: nothing is written past it
-      if (out_cap[i]) memcpy(out[i], hst + pos[2 * k], out_cap[i]);
-      continue;
-    }
-    memcpy(out[i], hst + pos[2 * k], len);
-  }
-  return 0;
+  return enc_finish(st, alloc, actx, hst, dpos, nd,
+                    "PNG encode: a band's block did not have the size its codes were chosen for", dpack, bound_total,
+                    "PNG", desc_img, out, out_cap, out_len, status, true, err);
 }
 }  // namespace fi

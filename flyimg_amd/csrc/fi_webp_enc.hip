@@ -24,7 +24,8 @@
 //            offset mod 32; whole dwords -> the slot with plain stores, the
 //            band's first dword and its last partial dword with atomic OR (bands
 //            are not byte aligned in VP8L: neighbours share those dwords);
-//   k_webp_pack   exclusive scan of the file sizes, slots -> one contiguous
+//   k_webp_pack   exclusive scan of the file sizes (k_webp_scan: the scan of
+//            fi_enc_pack.h with an image as the item), slots -> one contiguous
 //            stream, which the host fetches with one copy.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +35,8 @@
 #include <string>
 #include <vector>
 
+#include "fi_enc_batch.h"
+#include "fi_enc_pack.h"
 #include "fi_internal.h"
 #define FI_WEBP_DEVICE 1
 #include "fi_webp_enc.h"
@@ -193,38 +196,23 @@ __global__ __launch_bounds__(256) void k_webp_emit(const WebpImg *__restrict__ d
   if (!ok) *fault = 1;
 }
 
-__global__ void k_webp_scan(const WebpImg *__restrict__ descs, const WebpImgOut *__restrict__ outs, int nimg,
-                            int64_t *__restrict__ imgpos) {
-  if (blockIdx.x || threadIdx.x) return;
-  int64_t acc = 0;
-  for (int k = 0; k < nimg; k++) {
-    imgpos[2 * k] = acc;
-    acc += std::min(outs[k].file_bytes, descs[k].slot_bytes);
-    imgpos[2 * k + 1] = acc;
-  }
+// every image is one item: its file, clamped to its slot
+__global__ __launch_bounds__(256) void k_webp_scan(const WebpImg *__restrict__ descs,
+                                                   const WebpImgOut *__restrict__ outs, int nimg,
+                                                   int64_t *__restrict__ imgpos) {
+  enc_scan_items(
+      nimg, [=](int k) { return EncItem{std::min(outs[k].file_bytes, descs[k].slot_bytes), k, true, true}; }, nullptr,
+      imgpos);
 }
 
-// blockIdx.x: the image, blockIdx.y: its share of the copy (dword stores once the destination is aligned)
+// blockIdx.x: the image, blockIdx.y: its share of the copy
 __global__ __launch_bounds__(256) void k_webp_pack(const WebpImg *__restrict__ descs, int nimg,
                                                    const int64_t *__restrict__ imgpos,
                                                    const uint8_t *__restrict__ slots, uint8_t *__restrict__ packed) {
   const int img = blockIdx.x;
   if (img >= nimg) return;
-  const int64_t n = imgpos[2 * img + 1] - imgpos[2 * img];
-  uint8_t *dst = packed + imgpos[2 * img];
-  const uint8_t *s = slots + descs[img].slot0;
-  const int64_t t = (int64_t)blockIdx.y * 256 + threadIdx.x, step = (int64_t)gridDim.y * 256;
-  const int64_t head = std::min<int64_t>(n, (int64_t)((4 - (reinterpret_cast<uintptr_t>(dst) & 3)) & 3));
-  if (t < head) dst[t] = s[t];
-  const int64_t nw = (n - head) >> 2;
-  uint32_t *dw = reinterpret_cast<uint32_t *>(dst + head);
-  const uint8_t *sw = s + head;
-  for (int64_t i = t; i < nw; i += step) {
-    const uint8_t *p = sw + 4 * i;
-    dw[i] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-  }
-  const int64_t tail0 = head + 4 * nw;
-  if (t < n - tail0) dst[tail0 + t] = s[tail0 + t];
+  enc_copy_aligned(packed + imgpos[2 * img], slots + descs[img].slot0, imgpos[2 * img + 1] - imgpos[2 * img],
+                   (int64_t)blockIdx.y * 256 + threadIdx.x, (int64_t)gridDim.y * 256);
 }
 
 // ---------------------------------------------------------------------------
@@ -239,13 +227,11 @@ int webp_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
   std::vector<int> desc_img;
   std::vector<WebpBandRef> bands;
   int64_t nblocks = 0, npix = 0, slot_total = 0;
-  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
   for (int i = 0; i < n; i++) {
     out_len[i] = 0;
     const int p = predictor ? predictor[i] : -1;
-    status[i] = webp_enc_check(w[i], h[i], channels[i], p);
-    if (!status[i] && (!src[i] || src_stride[i] < (int64_t)w[i] * channels[i] || (out_cap[i] && !out[i])))
-      status[i] = FI_EINVAL;
+    status[i] = enc_io_status(webp_enc_check(w[i], h[i], channels[i], p), src[i], src_stride[i], w[i], channels[i],
+                              out[i], out_cap[i]);
     if (status[i]) continue;
     size_t bnd = 0;
     (void)webp_enc_bound(w[i], h[i], channels[i], &bnd);
@@ -280,21 +266,24 @@ int webp_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
   if (descs.empty()) return 0;
   const int nd = (int)descs.size(), nb = (int)bands.size();
   // upload: descriptors, bands
-  const size_t o_desc = 0, o_band = o_desc + up256(descs.size() * sizeof(WebpImg));
-  const size_t up_total = o_band + up256(bands.size() * sizeof(WebpBandRef));
+  EncArena up, work;
+  const size_t o_desc = up.add(descs.size() * sizeof(WebpImg));
+  const size_t o_band = up.add(bands.size() * sizeof(WebpBandRef));
+  const size_t up_total = up.total();
   // work: residuals, tokens, modes, token counts, band histograms, band offsets, code tables, decisions,
   // [zeroed from here] image histograms, positions + fault word, slots
-  const size_t k_resid = 0, k_tok = k_resid + up256((size_t)npix * 4);
-  const size_t k_modes = k_tok + up256((size_t)npix * 4);
-  const size_t k_ntok = k_modes + up256((size_t)nblocks);
-  const size_t k_bhist = k_ntok + up256((size_t)nb * 4);
-  const size_t k_boff = k_bhist + up256((size_t)nb * kWebpHist * 4);
-  const size_t k_tabs = k_boff + up256((size_t)nb * 8);
-  const size_t k_outs = k_tabs + up256((size_t)nd * kWebpHist * 4);
-  const size_t k_ihist = k_outs + up256((size_t)nd * sizeof(WebpImgOut));
-  const size_t k_pos = k_ihist + up256((size_t)nd * kWebpHist * 4);
-  const size_t k_slots = k_pos + up256((size_t)nd * 16 + 16);  // (+ the fault word behind the positions)
-  const size_t work_total = k_slots + (size_t)slot_total;
+  const size_t k_resid = work.add((size_t)npix * 4);
+  const size_t k_tok = work.add((size_t)npix * 4);
+  const size_t k_modes = work.add((size_t)nblocks);
+  const size_t k_ntok = work.add((size_t)nb * 4);
+  const size_t k_bhist = work.add((size_t)nb * kWebpHist * 4);
+  const size_t k_boff = work.add((size_t)nb * 8);
+  const size_t k_tabs = work.add((size_t)nd * kWebpHist * 4);
+  const size_t k_outs = work.add((size_t)nd * sizeof(WebpImgOut));
+  const size_t k_ihist = work.add((size_t)nd * kWebpHist * 4);
+  const size_t k_pos = work.add((size_t)nd * 16 + 16);  // (+ the fault word behind the positions)
+  const size_t k_slots = work.add((size_t)slot_total);
+  const size_t work_total = work.total();
   uint8_t *dup = (uint8_t *)alloc(actx, 0, up_total);
   uint8_t *hst = (uint8_t *)alloc(actx, 3, std::max(up_total, (size_t)nd * 16 + 16));
   uint8_t *dwork = (uint8_t *)alloc(actx, 1, work_total);
@@ -333,49 +322,11 @@ int webp_encode_batch(hipStream_t st, const uint8_t *const *src, const int32_t *
   hipLaunchKernelGGL(k_webp_emit, dim3((unsigned)nb), dim3(256), 0, st, dd, db, nb, dresid, dtok, dntok, dtabs, dboff,
                      douts, dslots, dfault);
   stage(actx, "k_webp_pack");
-  hipLaunchKernelGGL(k_webp_scan, dim3(1), dim3(64), 0, st, dd, douts, nd, dpos);
+  hipLaunchKernelGGL(k_webp_scan, dim3(1), dim3(256), 0, st, dd, douts, nd, dpos);
   hipLaunchKernelGGL(k_webp_pack, dim3((unsigned)nd, 16), dim3(256), 0, st, dd, nd, dpos, dslots, dpack);
   stage(actx, nullptr);
-  // the image positions, then exactly the packed bytes
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(hst, dpos, (size_t)nd * 16 + 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    *err = "WebP encode kernels";
-    return FI_EDEVICE;
-  }
-  std::vector<int64_t> pos((size_t)nd * 2);
-  memcpy(pos.data(), hst, (size_t)nd * 16);
-  int32_t fault = 0;
-  memcpy(&fault, hst + (size_t)nd * 16, 4);
-  if (fault) {
-    *err = "WebP encode: the bits emitted differ from the bits priced";
-    return FI_EDEVICE;
-  }
-  const int64_t total = pos[2 * (size_t)nd - 1];
-  if (total < 0 || total > slot_total) {
-    *err = "WebP encode: packed size out of range";
-    return FI_EDEVICE;
-  }
-  hst = (uint8_t *)alloc(actx, 3, (size_t)total);
-  if (!hst) {
-    *err = "pinned memory for the WebP encode download";
-    return FI_ENOMEM;
-  }
-  if (hipMemcpyAsync(hst, dpack, (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    *err = "WebP encode download";
-    return FI_EDEVICE;
-  }
-  for (int k = 0; k < nd; k++) {
-    const int i = desc_img[k];
-    const size_t len = (size_t)(pos[2 * k + 1] - pos[2 * k]);
-    out_len[i] = len;
-    if (len > out_cap[i]) {
-      status[i] = FI_ENOMEM;  // the caller's buffer is too small: nothing is written, as in the host form
-      continue;
-    }
-    memcpy(out[i], hst + pos[2 * k], len);
-  }
-  return 0;
+  // (a file longer than its buffer: nothing is written, as in the host form)
+  return enc_finish(st, alloc, actx, hst, dpos, nd, "WebP encode: the bits emitted differ from the bits priced", dpack,
+                    (size_t)slot_total, "WebP", desc_img, out, out_cap, out_len, status, false, err);
 }
 }  // namespace fi

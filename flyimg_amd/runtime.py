@@ -6,6 +6,7 @@ batches (``fi_process_batch_device``, used by bench.py).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from dataclasses import dataclass
 
@@ -446,8 +447,7 @@ class Context:
                 dims.append(jpeg_view_dims(i[0], i[1], v) + (i[2],) if i else None)
             infos = dims
         sizes = [(i[0] * i[1] * i[2]) if i else 1 for i in infos]
-        ptrs = [self.malloc(max(sz, 1)) for sz in sizes]
-        try:
+        with self._scratch(sizes) as ptrs:
             status = self.jpeg_decode(blobs, ptrs, [(i[0] * i[2]) if i else 1 for i in infos], progressive=progressive,
                                       views=views)
             out = []
@@ -459,9 +459,6 @@ class Context:
                 a = self.d2h(p, sz)
                 out.append(a.reshape(h, w, 3) if c == 3 else a.reshape(h, w))
             return out
-        finally:
-            for p in ptrs:
-                self.free(p)
 
     def png_decode(self, blobs: list[bytes], dptrs: list[int], strides: list[int], out_channels=None) -> list[int]:
         """fi_png_decode_device: decodes PNG byte strings into the device
@@ -495,8 +492,7 @@ class Context:
         ocs = list(out_channels) if isinstance(out_channels, (list, tuple)) else [out_channels or 0] * n
         infos = [png_info(b) for b in blobs]
         dims = [(i[0], i[1], oc or i[2]) if i else None for i, oc in zip(infos, ocs)]
-        ptrs = [self.malloc(max(d[0] * d[1] * d[2], 1) if d else 1) for d in dims]
-        try:
+        with self._scratch([d[0] * d[1] * d[2] if d else 1 for d in dims]) as ptrs:
             status = self.png_decode(blobs, ptrs, [d[0] * d[2] if d else 1 for d in dims], ocs)
             out = []
             for d, p, s in zip(dims, ptrs, status):
@@ -507,22 +503,82 @@ class Context:
                 a = self.d2h(p, w * h * c)
                 out.append(a.reshape(h, w) if c == 1 else a.reshape(h, w, c))
             return out
+
+    # ---- what the codec wrappers share ----------------------------------------
+    @contextlib.contextmanager
+    def _scratch(self, sizes):
+        """Device buffers of ``sizes`` bytes (at least 1), freed on the way out."""
+        ptrs = [self.malloc(max(sz, 1)) for sz in sizes]
+        try:
+            yield ptrs
         finally:
             for p in ptrs:
                 self.free(p)
 
-    def _jpeg_encode_call(self, views, qs, ss, ptrs, caps, progressive=False):
+    @contextlib.contextmanager
+    def _uploaded(self, images):
+        """Host arrays (HW, HWC) in scratch device buffers, as (device pointer,
+        w, h, stride, channels) views."""
+        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        with self._scratch([a.nbytes for a in arrs]) as ptrs:
+            views = []
+            for a, p in zip(arrs, ptrs):
+                self.h2d(p, a)
+                c = a.shape[2] if a.ndim == 3 else 1
+                views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
+            yield views
+
+    @staticmethod
+    def _per_image(value, n):
+        return list(value) if isinstance(value, (list, tuple)) else [value] * n
+
+    def _encode_call(self, fn, views, extras, ptrs, caps, *tail):
+        """fn = a fi_*_encode_device: the argument block they share, with the
+        codec's per-image int32 arrays ``extras`` (None: the NULL pointer)
+        behind the strides and ``tail`` behind the status."""
         n = len(views)
         I32, I64, SZ, VP = ctypes.c_int32 * n, ctypes.c_int64 * n, ctypes.c_size_t * n, ctypes.c_void_p * n
         out_len, status = SZ(), I32()
-        args = (self.h, VP(*[v[0] for v in views]), I32(*[v[1] for v in views]), I32(*[v[2] for v in views]),
-                I32(*[v[4] for v in views]), I64(*[v[3] for v in views]), I32(*qs), I32(*ss), n,
-                VP(*ptrs), SZ(*caps), out_len, status)
-        if progressive:
-            rc = self._lib.fi_jpeg_encode_device_ex(*args, L.FI_JPEG_ENC_PROGRESSIVE)
-        else:
-            rc = self._lib.fi_jpeg_encode_device(*args)
+        rc = fn(self.h, VP(*[v[0] for v in views]), I32(*[v[1] for v in views]), I32(*[v[2] for v in views]),
+                I32(*[v[4] for v in views]), I64(*[v[3] for v in views]),
+                *[I32(*e) if e is not None else None for e in extras], n, VP(*ptrs), SZ(*caps), out_len, status, *tail)
         return rc, list(status), list(out_len)
+
+    @staticmethod
+    def _encode_guarded(call, caps):
+        """call(ptrs, caps) into fresh buffers of caps[i] + 64 bytes whose last
+        128 are 0xA5: (rc, status list, length list, buffer list)."""
+        offs = np.concatenate([[0], np.cumsum([c + 64 for c in caps])]).astype(np.int64)
+        pool = np.empty(int(offs[-1]), np.uint8)
+        bufs = [pool[int(offs[i]):int(offs[i + 1])] for i in range(len(caps))]
+        for b, c in zip(bufs, caps):
+            b[max(0, c - 64):] = 0xA5
+        rc, status, lens = call([b.ctypes.data for b in bufs], caps)
+        return rc, status, lens, bufs
+
+    def _encode_pooled(self, call, caps, short_is_status=False):
+        """call(ptrs, caps) into the output pool all the encoders keep: (status
+        list, length list, files -- None where the status is not 0).  A
+        failure of the call, not of an image, raises (``short_is_status``:
+        FI_ENOMEM that an image reports is the image's)."""
+        offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+        pool = getattr(self, "_enc_out", None)
+        if pool is None or pool.size < int(offs[-1]):  # kept: fresh pages are the cost of a large buffer
+            pool = self._enc_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
+        base = pool.ctypes.data
+        rc, status, lens = call([base + int(o) for o in offs[:-1]], caps)
+        if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL) and not (
+                short_is_status and rc == L.FI_ENOMEM and rc in status):
+            L.check(rc)
+        files = [pool[int(offs[i]):int(offs[i]) + lens[i]].tobytes() if status[i] == L.FI_OK else None
+                 for i in range(len(caps))]
+        return status, lens, files
+
+    def _jpeg_encode_call(self, views, qs, ss, ptrs, caps, progressive=False):
+        if progressive:
+            return self._encode_call(self._lib.fi_jpeg_encode_device_ex, views, [qs, ss], ptrs, caps,
+                                     L.FI_JPEG_ENC_PROGRESSIVE)
+        return self._encode_call(self._lib.fi_jpeg_encode_device, views, [qs, ss], ptrs, caps)
 
     def _jpeg_bound(self, view, q, s, progressive=False):
         b = ctypes.c_size_t()
@@ -541,17 +597,11 @@ class Context:
         ``progressive``: fi_jpeg_encode_device_ex with FI_JPEG_ENC_PROGRESSIVE
         and its bound."""
         n = len(views)
-        qs = list(quality) if isinstance(quality, (list, tuple)) else [quality] * n
-        ss = list(subsampling) if isinstance(subsampling, (list, tuple)) else [subsampling] * n
+        qs, ss = self._per_image(quality, n), self._per_image(subsampling, n)
         if caps is None:
             caps = [self._jpeg_bound(v, q, s, progressive) for v, q, s in zip(views, qs, ss)]
-        offs = np.concatenate([[0], np.cumsum([c + 64 for c in caps])]).astype(np.int64)
-        pool = np.empty(int(offs[-1]), np.uint8)
-        bufs = [pool[int(offs[i]):int(offs[i + 1])] for i in range(n)]
-        for b, c in zip(bufs, caps):
-            b[max(0, c - 64):] = 0xA5
-        rc, status, lens = self._jpeg_encode_call(views, qs, ss, [b.ctypes.data for b in bufs], caps, progressive)
-        return rc, status, lens, bufs
+        return self._encode_guarded(lambda ptrs, caps: self._jpeg_encode_call(views, qs, ss, ptrs, caps, progressive),
+                                    caps)
 
     def jpeg_encode(self, views, quality, subsampling, progressive=False) -> list[bytes | None]:
         """fi_jpeg_encode_device: baseline JPEG files of device-resident images
@@ -569,19 +619,11 @@ class Context:
         n = len(views)
         if not n:
             return []
-        qs = list(quality) if isinstance(quality, (list, tuple)) else [quality] * n
-        ss = list(subsampling) if isinstance(subsampling, (list, tuple)) else [subsampling] * n
+        qs, ss = self._per_image(quality, n), self._per_image(subsampling, n)
         caps = [min(self._jpeg_bound(v, q, s, progressive), v[1] * v[2] * v[4] + 1024)
                 for v, q, s in zip(views, qs, ss)]
-        offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
-        pool = getattr(self, "_enc_out", None)  # the output pool of jpeg_encode and png_encode alike
-        if pool is None or pool.size < int(offs[-1]):  # kept: fresh pages are the cost of a large buffer
-            pool = self._enc_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
-        base = pool.ctypes.data
-        rc, status, lens = self._jpeg_encode_call(views, qs, ss, [base + int(o) for o in offs[:-1]], caps, progressive)
-        if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL) and not (rc == L.FI_ENOMEM and rc in status):
-            L.check(rc)  # a failure of the call, not of an image
-        files = [pool[int(offs[i]):int(offs[i]) + lens[i]].tobytes() if status[i] == L.FI_OK else None for i in range(n)]
+        status, lens, files = self._encode_pooled(
+            lambda ptrs, caps: self._jpeg_encode_call(views, qs, ss, ptrs, caps, progressive), caps, short_is_status=True)
         again = [i for i in range(n) if status[i] == L.FI_ENOMEM and lens[i] > caps[i]]
         if again:
             big = [np.empty(lens[i], np.uint8) for i in again]
@@ -597,28 +639,11 @@ class Context:
         """jpeg_encode of host arrays (HW, HWC with 1..4 channels), uploaded to
         scratch device buffers first (tests / tools): the counterpart of
         jpeg_decode_host."""
-        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
-        ptrs = [self.malloc(max(a.nbytes, 1)) for a in arrs]
-        try:
-            views = []
-            for a, p in zip(arrs, ptrs):
-                self.h2d(p, a)
-                c = a.shape[2] if a.ndim == 3 else 1
-                views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
+        with self._uploaded(images) as views:
             return self.jpeg_encode(views, quality, subsampling, progressive)
-        finally:
-            for p in ptrs:
-                self.free(p)
 
     def _png_encode_call(self, views, fs, ptrs, caps):
-        n = len(views)
-        I32, I64, SZ, VP = ctypes.c_int32 * n, ctypes.c_int64 * n, ctypes.c_size_t * n, ctypes.c_void_p * n
-        out_len, status = SZ(), I32()
-        rc = self._lib.fi_png_encode_device(
-            self.h, VP(*[v[0] for v in views]), I32(*[v[1] for v in views]), I32(*[v[2] for v in views]),
-            I32(*[v[4] for v in views]), I64(*[v[3] for v in views]), I32(*fs) if fs is not None else None, n,
-            VP(*ptrs), SZ(*caps), out_len, status)
-        return rc, list(status), list(out_len)
+        return self._encode_call(self._lib.fi_png_encode_device, views, [fs], ptrs, caps)
 
     def _png_bound(self, view):
         b = ctypes.c_size_t()
@@ -631,17 +656,10 @@ class Context:
         fi_png_encode_bound, 1 where the bound turns the image down).  Returns
         (rc, status list, length list, output buffer list) with the 0xA5
         guards of jpeg_encode_raw."""
-        n = len(views)
-        fs = None if filter is None else list(filter) if isinstance(filter, (list, tuple)) else [filter] * n
+        fs = None if filter is None else self._per_image(filter, len(views))
         if caps is None:
             caps = [self._png_bound(v) for v in views]
-        offs = np.concatenate([[0], np.cumsum([c + 64 for c in caps])]).astype(np.int64)
-        pool = np.empty(int(offs[-1]), np.uint8)
-        bufs = [pool[int(offs[i]):int(offs[i + 1])] for i in range(n)]
-        for b, c in zip(bufs, caps):
-            b[max(0, c - 64):] = 0xA5
-        rc, status, lens = self._png_encode_call(views, fs, [b.ctypes.data for b in bufs], caps)
-        return rc, status, lens, bufs
+        return self._encode_guarded(lambda ptrs, caps: self._png_encode_call(views, fs, ptrs, caps), caps)
 
     def png_encode(self, views, filter=-1) -> list[bytes | None]:
         """fi_png_encode_device: PNG files of device-resident images given as
@@ -650,46 +668,20 @@ class Context:
         0..4 fixed (per image or one value).  None where the encoder turned the
         image down.  The output buffers are sized to fi_png_encode_bound (a
         few hundred bytes above the pixels), so one call always suffices."""
-        n = len(views)
-        if not n:
+        if not len(views):
             return []
-        fs = list(filter) if isinstance(filter, (list, tuple)) else [filter] * n
-        caps = [self._png_bound(v) for v in views]
-        offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
-        pool = getattr(self, "_enc_out", None)  # the output pool of jpeg_encode and png_encode alike
-        if pool is None or pool.size < int(offs[-1]):  # kept: fresh pages are the cost of a large buffer
-            pool = self._enc_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
-        base = pool.ctypes.data
-        rc, status, lens = self._png_encode_call(views, fs, [base + int(o) for o in offs[:-1]], caps)
-        if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL):
-            L.check(rc)  # a failure of the call, not of an image
-        return [pool[int(offs[i]):int(offs[i]) + lens[i]].tobytes() if status[i] == L.FI_OK else None for i in range(n)]
+        fs = self._per_image(filter, len(views))
+        return self._encode_pooled(lambda ptrs, caps: self._png_encode_call(views, fs, ptrs, caps),
+                                   [self._png_bound(v) for v in views])[2]
 
     def png_encode_host(self, images: list[np.ndarray], filter=-1) -> list[bytes | None]:
         """png_encode of host arrays (HW, HWC with 1..4 channels), uploaded to
         scratch device buffers first (tests / tools)."""
-        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
-        ptrs = [self.malloc(max(a.nbytes, 1)) for a in arrs]
-        try:
-            views = []
-            for a, p in zip(arrs, ptrs):
-                self.h2d(p, a)
-                c = a.shape[2] if a.ndim == 3 else 1
-                views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
+        with self._uploaded(images) as views:
             return self.png_encode(views, filter)
-        finally:
-            for p in ptrs:
-                self.free(p)
 
     def _webp_encode_call(self, views, ps, ptrs, caps):
-        n = len(views)
-        I32, I64, SZ, VP = ctypes.c_int32 * n, ctypes.c_int64 * n, ctypes.c_size_t * n, ctypes.c_void_p * n
-        out_len, status = SZ(), I32()
-        rc = self._lib.fi_webp_encode_device(
-            self.h, VP(*[v[0] for v in views]), I32(*[v[1] for v in views]), I32(*[v[2] for v in views]),
-            I32(*[v[4] for v in views]), I64(*[v[3] for v in views]), I32(*ps) if ps is not None else None, n,
-            VP(*ptrs), SZ(*caps), out_len, status)
-        return rc, list(status), list(out_len)
+        return self._encode_call(self._lib.fi_webp_encode_device, views, [ps], ptrs, caps)
 
     def _webp_bound(self, view):
         b = ctypes.c_size_t()
@@ -702,17 +694,10 @@ class Context:
         fi_webp_encode_bound, 1 where the bound turns the image down).
         Returns (rc, status list, length list, output buffer list) with the
         0xA5 guards of jpeg_encode_raw."""
-        n = len(views)
-        ps = None if predictor is None else list(predictor) if isinstance(predictor, (list, tuple)) else [predictor] * n
+        ps = None if predictor is None else self._per_image(predictor, len(views))
         if caps is None:
             caps = [self._webp_bound(v) for v in views]
-        offs = np.concatenate([[0], np.cumsum([c + 64 for c in caps])]).astype(np.int64)
-        pool = np.empty(int(offs[-1]), np.uint8)
-        bufs = [pool[int(offs[i]):int(offs[i + 1])] for i in range(n)]
-        for b, c in zip(bufs, caps):
-            b[max(0, c - 64):] = 0xA5
-        rc, status, lens = self._webp_encode_call(views, ps, [b.ctypes.data for b in bufs], caps)
-        return rc, status, lens, bufs
+        return self._encode_guarded(lambda ptrs, caps: self._webp_encode_call(views, ps, ptrs, caps), caps)
 
     def webp_encode(self, views, predictor=-1) -> list[bytes | None]:
         """fi_webp_encode_device: lossless WebP files of device-resident
@@ -722,36 +707,17 @@ class Context:
         where the encoder turned the image down.  The output buffers are sized
         to fi_webp_encode_bound (below 1 KiB above the pixels), so one call
         always suffices."""
-        n = len(views)
-        if not n:
+        if not len(views):
             return []
-        ps = list(predictor) if isinstance(predictor, (list, tuple)) else [predictor] * n
-        caps = [self._webp_bound(v) for v in views]
-        offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
-        pool = getattr(self, "_enc_out", None)  # the output pool of jpeg_encode, png_encode and webp_encode alike
-        if pool is None or pool.size < int(offs[-1]):  # kept: fresh pages are the cost of a large buffer
-            pool = self._enc_out = np.empty(int(offs[-1]) + int(offs[-1]) // 4, np.uint8)
-        base = pool.ctypes.data
-        rc, status, lens = self._webp_encode_call(views, ps, [base + int(o) for o in offs[:-1]], caps)
-        if rc not in (L.FI_OK, L.FI_EUNSUPPORTED, L.FI_EINVAL):
-            L.check(rc)  # a failure of the call, not of an image
-        return [pool[int(offs[i]):int(offs[i]) + lens[i]].tobytes() if status[i] == L.FI_OK else None for i in range(n)]
+        ps = self._per_image(predictor, len(views))
+        return self._encode_pooled(lambda ptrs, caps: self._webp_encode_call(views, ps, ptrs, caps),
+                                   [self._webp_bound(v) for v in views])[2]
 
     def webp_encode_host(self, images: list[np.ndarray], predictor=-1) -> list[bytes | None]:
         """webp_encode of host arrays (HW, HWC with 1..4 channels), uploaded to
         scratch device buffers first (tests / tools)."""
-        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
-        ptrs = [self.malloc(max(a.nbytes, 1)) for a in arrs]
-        try:
-            views = []
-            for a, p in zip(arrs, ptrs):
-                self.h2d(p, a)
-                c = a.shape[2] if a.ndim == 3 else 1
-                views.append((p, a.shape[1], a.shape[0], a.shape[1] * c, c))
+        with self._uploaded(images) as views:
             return self.webp_encode(views, predictor)
-        finally:
-            for p in ptrs:
-                self.free(p)
 
     def process_device_resident(self, views, ops: list[Op]):
         """fi_process_batch_device on device-resident sources given as (device

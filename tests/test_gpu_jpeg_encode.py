@@ -260,3 +260,16 @@ def test_codec_pipeline_gpu_encode(ctx):
     assert ec == eb
     for i in range(7):
         _same(ea[i], _pillow(kept[eb[i]], quality[i], 0 if quality[i] >= 90 else 2), f"pipeline output {i}")
+
+
+def test_jpeg_encode_scan_chunk_carry(ctx):
+    """One call whose restart intervals cross the 256-item chunks of the
+    batch's scan (enc_scan_items): gray images of 254, 3 and 300 MCU rows, so
+    the second image's intervals are items 254..256 -- its start is written in
+    the first chunk, its end in the second, from the carried total -- and the
+    third image's run across the second boundary to item 556."""
+    images = [np.ascontiguousarray(synth_rgb(8, h, 70 + h)[..., 1]) for h in (2032, 24, 2400)]
+    assert [(-(-a.shape[0] // 8), a.shape[1]) for a in images] == [(254, 8), (3, 8), (300, 8)]
+    got = ctx.jpeg_encode_host(images, [90, 75, 85], 0)
+    for k, (a, q) in enumerate(zip(images, [90, 75, 85])):
+        _same(got[k], _pillow(a, q), f"image {k}: 8x{a.shape[0]} gray q{q}")

@@ -257,3 +257,37 @@ def _reference_files(ctx, blobs, opts, quality):
     by_file = {f: px for f, px in kept}
     return [_pillow(by_file[files[i]], quality[i], 0 if quality[i] >= 90 else 2)
             for i in range(len(blobs)) if files[i][:2] == b"\xff\xd8"]
+
+
+def _pieces(blob):
+    """The pieces jpeg_pencode_batch packs for this file: the head, per scan
+    its DHT segments, its DRI / SOS bytes and its restart intervals, EOI."""
+    ndht = nsos = nrst = 0
+    i = 2
+    while i < len(blob):
+        assert blob[i] == 0xFF
+        m = blob[i + 1]
+        if m == 0xD9:
+            break
+        ndht += m == 0xC4
+        i += 2 + int.from_bytes(blob[i + 2:i + 4], "big")
+        if m == 0xDA:  # entropy-coded data up to the next marker that is no RSTn
+            nsos += 1
+            while not (blob[i] == 0xFF and blob[i + 1] != 0 and not 0xD0 <= blob[i + 1] <= 0xD7):
+                nrst += blob[i] == 0xFF and 0xD0 <= blob[i + 1] <= 0xD7
+                i += 1
+    return 1 + ndht + nsos + (nrst + nsos) + 1
+
+
+def test_progressive_encode_pieces_cross_the_scan_chunk(ctx):
+    """One call whose pieces cross the 256-item chunk of the batch's scan
+    (enc_scan_items): 24 x 24 RGB 4:2:0 images have some 45 pieces each (10
+    scans; three images stay below 256), so eight of them."""
+    images = [synth_rgb(24, 24, 90 + k) for k in range(8)]
+    quality = [90, 75, 50, 95, 85, 60, 30, 100]
+    refs = [_pillow(a, q, 2) for a, q in zip(images, quality)]
+    npieces = [_pieces(r) for r in refs]
+    assert sum(npieces[:3]) < 256 < sum(npieces), npieces
+    got = ctx.jpeg_encode_host(images, quality, 2, progressive=True)
+    for k in range(8):
+        _same(got[k], refs[k], f"image {k} q{quality[k]}")

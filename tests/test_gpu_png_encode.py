@@ -462,3 +462,22 @@ def test_codec_pipeline_gpu_png(ctx):
         want = decode(res["enc"][i])
         assert want.shape[2] == 4 and want.shape[1] == 120
         _parse(res["png"][i], want)
+
+
+def test_png_encode_bands_across_the_scan_chunk(ctx):
+    """One call of 254 images of 4 x 4, a gray 300 x 220 image and 300 more of
+    4 x 4: the gray image's filtered stream is 66,220 bytes = 3 bands, the
+    items 254..256 of the batch's scan (enc_scan_items) on either side of its
+    first 256-item chunk; 557 bands cross the second.  Every file decodes to
+    its pixels and is the file the image gives in a call of its own."""
+    rgb = synth_rgb(4, 4 * 8, 77)
+    small = [_channels(np.ascontiguousarray(rgb[4 * k:4 * k + 4]), 1 + k % 4) for k in range(8)]
+    big = np.ascontiguousarray(synth_rgb(300, 220, 78)[..., 1])
+    assert 220 * (300 + 1) == 66220 and -(-66220 // BAND) == 3
+    images = [small[k % 8] for k in range(254)] + [big] + [small[(k + 3) % 8] for k in range(300)]
+    alone = {a.tobytes(): ctx.png_encode_host([a])[0] for a in small + [big]}
+    files = ctx.png_encode_host(images)
+    assert len(files) == 555
+    for k, (a, f) in enumerate(zip(images, files)):
+        assert f is not None and f == alone[a.tobytes()], k
+        assert np.array_equal(np.asarray(Image.open(io.BytesIO(f))), a), k

@@ -235,3 +235,21 @@ def test_codec_pipeline_gpu_webp(ctx):
         assert want.shape[1] == 100
         check_file(f, np.ascontiguousarray(want), literal=False)
     assert res["plain"][1][:2] == b"\xff\xd8"  # the opaque output without the switch: the option is ignored
+
+
+def test_webp_encode_300_tiny_images_cross_the_scan_chunk(ctx):
+    """One call of 300 images of 3 x 2 pixels, 1..4 channels in turn: the
+    images are the items of the batch's scan (enc_scan_items), so 300 of them
+    cross its 256-item chunk.  Their file lengths differ, and a RIFF file has an
+    even length, so the packed files start at both alignments a WebP file can
+    have, 0 and 2 mod 4, on either side of the chunk (the byte head and tail
+    of enc_copy_aligned; the odd alignments are the JPEG and PNG tests')."""
+    rng = np.random.default_rng(300)
+    images = [rng.integers(0, 256, (2, 3, 1 + k % 4), dtype=np.uint8) for k in range(300)]
+    files = ctx.webp_encode_host(images)
+    assert all(f is not None for f in files)
+    starts = np.concatenate([[0], np.cumsum([len(f) for f in files])])[:-1]
+    assert {int(s) % 4 for s in starts[:256]} == {0, 2} and {int(s) % 4 for s in starts[256:]} == {0, 2}
+    assert len({len(f) for f in files}) > 4
+    for k, (px, f) in enumerate(zip(images, files)):
+        assert f == webp_encode_host_form(px, -1), k
