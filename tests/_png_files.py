@@ -2,7 +2,9 @@
 tests/test_png_decode_cpu.py and tests/test_gpu_png_decode.py: chunks from
 ``struct`` and ``zlib.crc32``, a numpy restatement of the five row filters, and
 a bit-level deflate writer (fixed and dynamic Huffman blocks) for the streams
-zlib's own encoder never emits."""
+zlib's own encoder never emits.  For the encoder's tests
+(tests/test_gpu_png_encode.py, tests/test_gpu_lossless_content.py): a plain
+inflate that keeps every block's codes and symbols (``inflate_blocks``)."""
 import struct
 import zlib
 
@@ -270,3 +272,131 @@ def expand(symbols, prefix=b"") -> bytes:
 # lit/len lengths of a complete set: literals at 9 bits, the end of block at 2, length symbols
 # 257..260 (lengths 3..6) at 4
 LL_SIMPLE = [9] * 256 + [2] + [4] * 4
+
+
+# ---- inflate, symbol by symbol --------------------------------------------------------
+def check_code(lens, counts, what=""):
+    """What every prefix code a deflate block declares or uses must satisfy:
+    no length above 15, a complete Kraft sum where two or more symbols have a
+    code, every symbol that occurs has a code, and a symbol that occurs more
+    often never has the longer code."""
+    used = [l for l in lens if l]
+    assert max(lens, default=0) <= 15, what
+    if len(used) >= 2:
+        assert sum(1 << (15 - l) for l in used) == 1 << 15, (what, "Kraft sum")
+    by_len = {}
+    for s, n in enumerate(counts):
+        if n:
+            assert lens[s], (what, s)
+            by_len.setdefault(lens[s], []).append(n)
+    ls = sorted(by_len)
+    for a, b in zip(ls, ls[1:]):
+        assert min(by_len[a]) >= max(by_len[b]), (what, a, b)
+
+
+def inflate_blocks(payload):
+    """A plain inflate (RFC 1951) of a zlib stream that keeps what it read: per
+    block a dict of btype, final, ll_lens / d_lens (the code lengths; the fixed
+    codes' for btype 1, None for a stored block), stored (bytes of a stored
+    block), symbols -- (symbol number, value) with value the literal byte,
+    None for the end of block, or (length, distance, distance symbol) -- and
+    ll_counts / d_counts.  Returns (blocks, decoded bytes).  Every dynamic
+    block's codes go through ``check_code``."""
+    bits = "".join(format(x, "08b")[::-1] for x in payload[2:-4])
+    pos = 0
+
+    def get(n):
+        nonlocal pos
+        v = int(bits[pos:pos + n][::-1], 2) if n else 0
+        pos += n
+        return v
+
+    def table(lens):
+        codes, code = {}, 0
+        for ln in range(1, 16):
+            for s, l in enumerate(lens):
+                if l == ln:
+                    codes[format(code, f"0{ln}b")] = s
+                    code += 1
+            code <<= 1
+        return codes
+
+    def sym(codes):
+        nonlocal pos
+        c = ""
+        while c not in codes:
+            c += bits[pos]
+            pos += 1
+            assert len(c) <= 15
+        return codes[c]
+
+    blocks, out, final = [], bytearray(), 0
+    while not final:
+        final, btype = get(1), get(2)
+        blk = {"btype": btype, "final": final, "ll_lens": None, "d_lens": None, "stored": 0, "symbols": [],
+               "ll_counts": [0] * 288, "d_counts": [0] * 32}
+        if btype == 0:
+            pos = (pos + 7) // 8 * 8
+            n = get(16)
+            assert get(16) == n ^ 0xFFFF
+            out += bytes(int(bits[pos + 8 * i:pos + 8 * i + 8][::-1], 2) for i in range(n))
+            pos += 8 * n
+            blk["stored"] = n
+        else:
+            if btype == 1:
+                ll_lens, d_lens = list(FIXED_LL), list(FIXED_D)
+            else:
+                assert btype == 2
+                hlit, hdist, hclen = get(5) + 257, get(5) + 1, get(4) + 4
+                cl = [0] * 19
+                for i in range(hclen):
+                    cl[CL_ORDER[i]] = get(3)
+                clt, lens = table(cl), []
+                while len(lens) < hlit + hdist:
+                    v = sym(clt)
+                    if v < 16:
+                        lens.append(v)
+                    elif v == 16:
+                        lens += [lens[-1]] * (3 + get(2))
+                    elif v == 17:
+                        lens += [0] * (3 + get(3))
+                    else:
+                        lens += [0] * (11 + get(7))
+                assert len(lens) == hlit + hdist
+                ll_lens, d_lens = lens[:hlit] + [0] * (288 - hlit), lens[hlit:] + [0] * (32 - hdist)
+            blk["ll_lens"], blk["d_lens"] = ll_lens, d_lens
+            ll, dd = table(ll_lens), table(d_lens)
+            while True:
+                v = sym(ll)
+                blk["ll_counts"][v] += 1
+                if v < 256:
+                    out.append(v)
+                    blk["symbols"].append((v, v))
+                elif v == 256:
+                    blk["symbols"].append((v, None))
+                    break
+                else:
+                    assert v <= 285
+                    ln = LBASE[v - 257] + get(LEXT[v - 257])
+                    d = sym(dd)
+                    assert d <= 29
+                    blk["d_counts"][d] += 1
+                    dist = DBASE[d] + get(DEXT[d])
+                    assert dist <= len(out)
+                    for _ in range(ln):
+                        out.append(out[-dist])
+                    blk["symbols"].append((v, (ln, dist, d)))
+            if btype == 2:
+                check_code(ll_lens, blk["ll_counts"], "lit/len")
+                if sum(1 for l in d_lens if l) > 1 or sum(blk["d_counts"]):
+                    check_code(d_lens, blk["d_counts"], "distance")
+        blocks.append(blk)
+    assert (pos + 7) // 8 == len(payload) - 6
+    return blocks, bytes(out)
+
+
+def deflate_matches(payload):
+    """The (length, distance) pairs of every block of a zlib stream and the
+    decoded length (``inflate_blocks``, the matches alone)."""
+    blocks, out = inflate_blocks(payload)
+    return [[(v[0], v[1]) for s, v in b["symbols"] if s > 256] for b in blocks], len(out)

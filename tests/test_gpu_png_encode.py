@@ -5,7 +5,9 @@ must return the input pixels bit for bit.  On top: the adaptive filter choice
 against a numpy restatement of its rule, the deflate quality against zlib's
 Huffman-only coding of the same filtered stream, strided views, mixed batches
 with rejected images, the capacity rule, the pipeline switch and the kernel
-statistics."""
+statistics.  Crafted content -- deep codes, the length and distance ladders,
+the three block forms -- is in tests/_lossless_content.py and
+tests/test_gpu_lossless_content.py."""
 import io
 import os
 import struct
@@ -18,6 +20,8 @@ from PIL import Image
 from flyimg_amd import _lib as L
 from flyimg_amd.runtime import Context, png_encode_bound
 from flyimg_amd.synth import synth_rgb
+
+from ._png_files import deflate_matches as _deflate_matches
 
 pytestmark = pytest.mark.gpu
 
@@ -190,93 +194,6 @@ def test_png_encode_noise_is_stored_within_the_bound(ctx):
     for f, px in zip(files, images):
         payload, stream = _parse(f, px)  # (checks len(f) <= png_encode_bound)
         assert len(f) > len(stream)      # nothing to gain: stored blocks
-
-
-def _deflate_matches(payload):
-    """The (length, distance) pairs of every block of a zlib stream, by a plain
-    inflate of its symbols (RFC 1951), and the decoded length."""
-    bits = "".join(format(x, "08b")[::-1] for x in payload[2:-4])
-    pos = 0
-
-    def get(n):
-        nonlocal pos
-        v = int(bits[pos:pos + n][::-1], 2) if n else 0
-        pos += n
-        return v
-
-    def table(lens):
-        codes, code = {}, 0
-        for ln in range(1, 16):
-            for sym, l in enumerate(lens):
-                if l == ln:
-                    codes[format(code, f"0{ln}b")] = sym
-                    code += 1
-            code <<= 1
-        return codes
-
-    def sym(codes):
-        nonlocal pos
-        c = ""
-        while c not in codes:
-            c += bits[pos]
-            pos += 1
-            assert len(c) <= 15
-        return codes[c]
-
-    lbase = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
-    lext = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
-    dbase = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097,
-             6145, 8193, 12289, 16385, 24577]
-    dext = [0, 0, 0, 0] + [e for e in range(1, 14) for _ in range(2)]
-    order = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
-    blocks, total, final = [], 0, 0
-    while not final:
-        final, btype = get(1), get(2)
-        matches = []
-        if btype == 0:
-            pos = (pos + 7) // 8 * 8
-            n = get(16)
-            assert get(16) == n ^ 0xFFFF
-            pos += 8 * n
-            total += n
-        else:
-            if btype == 1:
-                ll = table([8] * 144 + [9] * 112 + [7] * 24 + [8] * 8)
-                dd = table([5] * 32)
-            else:
-                assert btype == 2
-                hlit, hdist, hclen = get(5) + 257, get(5) + 1, get(4) + 4
-                cl = [0] * 19
-                for i in range(hclen):
-                    cl[order[i]] = get(3)
-                clt, lens = table(cl), []
-                while len(lens) < hlit + hdist:
-                    v = sym(clt)
-                    if v < 16:
-                        lens.append(v)
-                    elif v == 16:
-                        lens += [lens[-1]] * (3 + get(2))
-                    elif v == 17:
-                        lens += [0] * (3 + get(3))
-                    else:
-                        lens += [0] * (11 + get(7))
-                assert len(lens) == hlit + hdist
-                ll, dd = table(lens[:hlit]), table(lens[hlit:])
-            while True:
-                v = sym(ll)
-                if v < 256:
-                    total += 1
-                elif v == 256:
-                    break
-                else:
-                    ln = lbase[v - 257] + get(lext[v - 257])
-                    d = sym(dd)
-                    dist = dbase[d] + get(dext[d])
-                    assert dist <= total
-                    matches.append((ln, dist))
-                    total += ln
-        blocks.append(matches)
-    return blocks, total
 
 
 def test_png_encode_match_distances(ctx):

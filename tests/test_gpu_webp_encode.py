@@ -3,7 +3,10 @@ fi_debug_webp_encode_host runs the same inline code on the CPU and is the
 specification: every device file must equal it byte for byte, and Pillow
 (libwebp) must return the input pixels.  On top: forced predictors, strided
 views, mixed batches with rejected images, the capacity rule, the kernel
-statistics, the size against the GPU PNG encoder and the pipeline switch."""
+statistics, the size against the GPU PNG encoder and the pipeline switch.  Crafted content
+-- codes the 15-bit limit shapes, literals above 48 bits, the length and
+distance ladders, band edges -- is in tests/_lossless_content.py,
+tests/test_lossless_content_cpu.py and tests/test_gpu_lossless_content.py."""
 import io
 import os
 

@@ -131,19 +131,30 @@ def read_image(br, w, h, main):
     codes = {name: read_code(br, n) for name, n in ALPHABETS}
     px = []
     st = {"literals": 0, "matches": 0, "distances": [], "lengths": [], "forms": {k: c.form for k, c in codes.items()},
-          "used": {k: len(c.used) for k, c in codes.items()}}
+          "used": {k: len(c.used) for k, c in codes.items()},
+          "code_lengths": {k: list(c.lengths) for k, c in codes.items()},
+          "counts": {k: [0] * n for k, n in ALPHABETS}, "tokens": []}
+    cnt = st["counts"]
     total = w * h
     while len(px) < total:
+        at = br.pos
         g = codes["green"].read(br)
+        cnt["green"][g] += 1
         if g < 256:
             r = codes["red"].read(br)
             b = codes["blue"].read(br)
             a = codes["alpha"].read(br)
             px.append((a << 24) | (r << 16) | (g << 8) | b)
             st["literals"] += 1
+            cnt["red"][r] += 1
+            cnt["blue"][b] += 1
+            cnt["alpha"][a] += 1
+            st["tokens"].append(("literal", at, br.pos - at))
         else:
             length = prefix_value(g - 256, br)
-            code = prefix_value(codes["dist"].read(br), br)
+            ds = codes["dist"].read(br)
+            cnt["dist"][ds] += 1
+            code = prefix_value(ds, br)
             if code <= 120:
                 raise Unsupported("short distance code")
             d = code - 120
@@ -154,7 +165,26 @@ def read_image(br, w, h, main):
             st["matches"] += 1
             st["distances"].append(d)
             st["lengths"].append(length)
+            st["tokens"].append(("copy", at, br.pos - at))
+    for k, c in codes.items():
+        check_frequency_order(cnt[k], c.lengths, k)
     return px, st
+
+
+def check_frequency_order(counts, lengths, what=""):
+    """A symbol that occurs more often never has the longer code (what any
+    Huffman construction, length-limited or not, guarantees)."""
+    by_len = {}
+    for s, n in enumerate(counts):
+        if n:
+            if not lengths[s] and sum(1 for v in counts if v) > 1:
+                raise ValueError("%s: symbol %d occurs without a code" % (what, s))
+            by_len.setdefault(lengths[s], []).append(n)
+    ls = sorted(by_len)
+    for a, b in zip(ls, ls[1:]):  # every count at a shorter length >= every count at a longer one
+        if min(by_len[a]) < max(by_len[b]):
+            raise ValueError("%s: a count of %d at %d bits, one of %d at %d bits" % (what, min(by_len[a]), a,
+                                                                                       max(by_len[b]), b))
 
 
 def _avg2(a, b):
@@ -242,7 +272,12 @@ def unpredict(px, w, h, modes, mw, bits):
 def decode(blob):
     """-> dict: pixels (h, w, 4) RGBA uint8, alpha_used, transforms (in written
     order), modes ((mh, mw) array or None), stats of the main image (literals,
-    matches, distances, lengths, forms, used), mode_stats, payload bits used."""
+    matches, distances, lengths, forms, used; code_lengths and counts: per
+    code the length and the number of occurrences of every symbol; tokens:
+    (kind, first payload bit, bits) of every literal and copy in stream
+    order), mode_stats, payload bits used.  Every code read is checked: no
+    length above 15, a complete Kraft sum, and no symbol that occurs more often
+    than another with a longer code."""
     if len(blob) < 20 or blob[:4] != b"RIFF" or blob[8:12] != b"WEBP":
         raise ValueError("no RIFF/WEBP container")
     if int.from_bytes(blob[4:8], "little") != len(blob) - 8:
