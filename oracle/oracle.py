@@ -118,6 +118,10 @@ def lib():
         L.or_hilbert_d2xy.restype = None
         L.or_mono_curve_level.argtypes = [i, i]
         L.or_mono_quant_info.argtypes = [P(ctypes.c_uint64), P(i), u16p, u16p]
+        L.or_mono_levels.argtypes = [P(ctypes.c_uint64), ctypes.c_long, P(i), P(i)]
+        L.or_mono_levels.restype = None
+        L.or_mono_stretch.argtypes = [ctypes.c_uint, i, i]
+        L.or_mono_stretch.restype = ctypes.c_uint
         assert L.or_sizeof_crop() == ctypes.sizeof(ScCrop)
         assert L.or_sizeof_params() == ctypes.sizeof(ScParams)
         _lib = L
@@ -182,6 +186,19 @@ def hilbert_d2xy(level: int, d: int):
 
 def mono_curve_level(w: int, h: int) -> int:
     return lib().or_mono_curve_level(w, h)
+
+
+def mono_levels(hist: np.ndarray):
+    """NormalizeImage's (black, white) of a Q16 gray histogram (or_mono_levels)."""
+    H = np.ascontiguousarray(hist, dtype=np.uint64)
+    assert H.size == 65536
+    b, w = ctypes.c_int(), ctypes.c_int()
+    lib().or_mono_levels(H.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(H.sum()), ctypes.byref(b), ctypes.byref(w))
+    return b.value, w.value
+
+
+def mono_stretch(q: int, black: int, white: int) -> int:
+    return lib().or_mono_stretch(int(q), black, white)
 
 
 def mono_quant_info(hist: np.ndarray):

@@ -61,7 +61,7 @@ class Node:
         self.color = -1
 
 
-def stretch(g: np.ndarray) -> np.ndarray:
+def stretch(g: np.ndarray, info=None) -> np.ndarray:
     n = g.size
     hist = np.bincount(g.ravel(), minlength=65536)
     bp, wp = n * 0.0015, n * 0.9995
@@ -81,6 +81,8 @@ def stretch(g: np.ndarray) -> np.ndarray:
             break
         i -= 1
     white = float(i)
+    if info is not None:
+        info["black"], info["white"] = int(black), int(white)
     if black == white:
         return g.copy()
     out = np.empty_like(g)
@@ -97,15 +99,26 @@ def stretch(g: np.ndarray) -> np.ndarray:
     return out
 
 
-def monochrome(g: np.ndarray, exact_sums: bool = False) -> np.ndarray:
+def monochrome(g: np.ndarray, exact_sums: bool = False, info=None) -> np.ndarray:
     """IM's -monochrome on a Q16 gray image -> 0/255.  exact_sums=True holds
     the leaf colour sums as exact integers (the oracle's reformulation);
-    False accumulates count * QuantumScale * pixel in raster order as IM does."""
+    False accumulates count * QuantumScale * pixel in raster order as IM does.
+    info, when a dict, is filled with what the run met: "bilevel" (the
+    pass-through was taken; nothing else is set then), "black", "white",
+    "cmap" (the colormap in DefineImageColormap's order), "clamp_lo" /
+    "clamp_hi" (dithered values the clamp moved to 0 / 65535), "stale" (pixels
+    the cache answered with another colour than a fresh search would have
+    picked) and "excluded" (pixels whose search subtree did not hold the
+    colour a search from the root picks)."""
     g = np.asarray(g, dtype=np.uint16)
     h, w = g.shape
     if np.all((g == 0) | (g == 65535)):
+        if info is not None:
+            info["bilevel"] = True
         return np.where(g > 0, 255, 0).astype(np.uint8)
-    s = stretch(g)
+    s = stretch(g, info)
+    if info is not None:
+        info.update(bilevel=False, clamp_lo=0, clamp_hi=0, stale=0, excluded=0)
     root = Node(None, 0, 0)
     nodes = [1]
     colors = [0]
@@ -204,6 +217,8 @@ def monochrome(g: np.ndarray, exact_sums: bool = False) -> np.ndarray:
             node.color = len(cmap) - 1
 
     define(root)
+    if info is not None:
+        info["cmap"] = list(cmap)
     # Riemersma dither
     wts = [0.0] * 16
     weight = 1.0
@@ -231,25 +246,35 @@ def monochrome(g: np.ndarray, exact_sums: bool = False) -> np.ndarray:
                         best[0] = d
                         best[1] = node.color
 
+    def search(c8, pv, from_root=False):
+        node = root
+        for index in range(7, 0, -1):
+            idn = 7 if (c8 >> index) & 1 else 0
+            if node.child[idn] is None:
+                break
+            node = node.child[idn]
+        best = [4.0 * (QR + 1.0) * (QR + 1.0) + 1.0, 0]
+        closest(root if from_root else node.parent, pv, best)
+        return best[1]
+
     def dither(direction):
         x, y = cur["x"], cur["y"]
         if 0 <= x < w and 0 <= y < h:
             pv = float(s[y, x])
             for i in range(16):
                 pv += wts[i] * err[i]
+            if info is not None:
+                info["clamp_lo"] += pv < 0.0
+                info["clamp_hi"] += pv > QR
             pv = float(clamp_pixel(pv))
             c8 = q2c(int(pv))
             key = c8 >> 2
+            if info is not None:
+                fresh = search(c8, pv)
+                info["stale"] += cache[key] >= 0 and cache[key] != fresh
+                info["excluded"] += fresh != search(c8, pv, from_root=True)
             if cache[key] < 0:
-                node = root
-                for index in range(7, 0, -1):
-                    idn = 7 if (c8 >> index) & 1 else 0
-                    if node.child[idn] is None:
-                        break
-                    node = node.child[idn]
-                best = [4.0 * (QR + 1.0) * (QR + 1.0) + 1.0, 0]
-                closest(node.parent, pv, best)
-                cache[key] = best[1]
+                cache[key] = search(c8, pv)
             idx = cache[key]
             out[y, x] = 255 if bilevel[idx] else 0
             del err[0]
