@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "fi_enc_batch.h"
+#include "fi_enc_dev.h"
 #include "fi_enc_pack.h"
 #include "fi_internal.h"
 #include "fi_jpeg_enc.h"
@@ -282,15 +283,7 @@ __global__ __launch_bounds__(256) void k_jpeg_fdct(const JpegEncDesc *__restrict
   for (int i = threadIdx.x; i < 512; i += 256) aclen[i] = (uint8_t)(huff[256 + 512 * (i >> 8) + (i & 255)] >> 16);
   __syncthreads();
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nblocks; i += (int64_t)gridDim.x * 256) {
-    int lo = 0, hi = nimg;  // image of block i
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (descs[mid].blk0 <= i)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    const JpegEncDesc D = descs[lo];
+    const JpegEncDesc D = descs[enc_find_image(descs, nimg, i, &JpegEncDesc::blk0)];
     const int64_t b = i - D.blk0;
     const int mcu = (int)(b / D.bpm), k = (int)(b - (int64_t)mcu * D.bpm);
     const int my = mcu / D.mcux, mx = mcu - my * D.mcux;
@@ -307,16 +300,6 @@ void jpeg_enc_launch_fdct(hipStream_t st, const JpegEncDesc *descs, int nimg, in
                           const uint32_t *huff, int16_t *coef, uint16_t *acbits) {
   hipLaunchKernelGGL(k_jpeg_fdct, dim3((unsigned)std::min<int64_t>((nblocks + 255) / 256, 1 << 20)), dim3(256), 0, st,
                      descs, nimg, nblocks, qts, huff, coef, acbits);
-}
-
-__device__ __forceinline__ int jpeg_enc_scan64(int v) {  // inclusive prefix sum over the wave
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
 }
 
 __global__ __launch_bounds__(64) void k_jpeg_henc(const JpegEncDesc *__restrict__ descs,
@@ -354,7 +337,7 @@ __global__ __launch_bounds__(64) void k_jpeg_henc(const JpegEncDesc *__restrict_
       (void)jpeg_enc_dc(tab + (comp ? 512 : 0), (int)coef[(b0 + j) * 64] - pdc, &dl);
       len = dl + acbits[b0 + j];
     }
-    const int incl = jpeg_enc_scan64(len);
+    const int incl = enc_scan64(len);
     int total = carry_bits + __shfl(incl, 63, 64);
     if (on) {
       JpegBitW bw;
@@ -378,7 +361,7 @@ __global__ __launch_bounds__(64) void k_jpeg_henc(const JpegEncDesc *__restrict_
       const uint32_t word = nv ? bits[w] : 0u;
       int nff = 0;
       for (int t = 0; t < nv; t++) nff += ((word >> (24 - 8 * t)) & 255u) == 255u;
-      const int incl_ff = jpeg_enc_scan64(nff);
+      const int incl_ff = enc_scan64(nff);
       int64_t o = (int64_t)outpos + 4 * w + ffs + (incl_ff - nff);
       for (int t = 0; t < nv; t++) {
         const uint8_t b = (uint8_t)(word >> (24 - 8 * t));

@@ -15,7 +15,7 @@
 #include <utility>
 #include <vector>
 
-#include "fi_png_enc.h"
+#include "fi_png_sum.h"
 
 // FI_PNG_UNI marks a value every lane holds alike (read from LDS at a uniform
 // address): the compiler then keeps the bit buffer, the positions and the
@@ -53,7 +53,7 @@ int png_out_channels(const PngSrc &S, int out_channels, int *outc);
 
 // ---- the inflater -------------------------------------------------------------------
 // CMF / FLG as zlib's inflate takes them: deflate, a window up to 32 KiB, the check bits, no dictionary
-FI_PNG_HD bool png_zlib_header_ok(uint32_t cmf, uint32_t flg) {
+FI_ENC_HD bool png_zlib_header_ok(uint32_t cmf, uint32_t flg) {
   return (cmf & 15u) == 8u && (cmf >> 4) <= 7u && !(flg & 0x20u) && ((cmf << 8) | flg) % 31u == 0u;
 }
 constexpr int kPngRing = 32768;      // the window, a ring
@@ -90,7 +90,7 @@ struct alignas(16) PngDecTabs {  // per wave, in LDS on the device
 struct PngHostIn {
   const uint8_t *p;
   uint32_t n;
-  FI_PNG_HD uint32_t word(uint32_t pos) const {
+  FI_ENC_HD uint32_t word(uint32_t pos) const {
     uint32_t v = 0;
     for (uint32_t k = 0; k < 4; k++)
       if (pos + k < n) v |= (uint32_t)p[pos + k] << (8 * k);
@@ -103,7 +103,7 @@ struct PngWalk {
   int32_t first, index;
   int32_t cnt[15 - kPngPrimBits];
 };
-FI_PNG_HD PngWalk png_walk_init(const uint16_t *count) {
+FI_ENC_HD PngWalk png_walk_init(const uint16_t *count) {
   PngWalk W;
   W.first = 0;
   W.index = 0;
@@ -120,13 +120,13 @@ FI_PNG_HD PngWalk png_walk_init(const uint16_t *count) {
 struct PngHostLook {
   const PngDecTabs *T;
   PngWalk lw, dw;
-  FI_PNG_HD void load(const PngDecTabs *t, int) {
+  FI_ENC_HD void load(const PngDecTabs *t, int) {
     T = t;
     lw = png_walk_init(t->lcount);
     dw = png_walk_init(t->dcount);
   }
-  FI_PNG_HD uint32_t lprim(uint32_t i) const { return T->lprim[i]; }
-  FI_PNG_HD uint32_t dprim(uint32_t i) const { return T->dprim[i]; }
+  FI_ENC_HD uint32_t lprim(uint32_t i) const { return T->lprim[i]; }
+  FI_ENC_HD uint32_t dprim(uint32_t i) const { return T->dprim[i]; }
 };
 
 template <class In>
@@ -136,33 +136,33 @@ struct PngBits {
   uint32_t pos;  // bytes taken into buf (virtual zero bytes behind the end included)
   uint64_t buf;
   int cnt;
-  FI_PNG_HD void fill() {  // >= 33 bits: a code of 15 bits and its 13 extra bits, or a stored block's LEN / NLEN
+  FI_ENC_HD void fill() {  // >= 33 bits: a code of 15 bits and its 13 extra bits, or a stored block's LEN / NLEN
     if (cnt <= 32) {
       buf |= (uint64_t)in.word(pos) << cnt;
       pos += 4;
       cnt += 32;
     }
   }
-  FI_PNG_HD uint32_t peek(int nb) const { return (uint32_t)(buf & ((1ull << nb) - 1ull)); }
-  FI_PNG_HD void drop(int nb) {
+  FI_ENC_HD uint32_t peek(int nb) const { return (uint32_t)(buf & ((1ull << nb) - 1ull)); }
+  FI_ENC_HD void drop(int nb) {
     buf >>= nb;
     cnt -= nb;
   }
-  FI_PNG_HD uint32_t take(int nb) {  // nb <= 32, after fill()
+  FI_ENC_HD uint32_t take(int nb) {  // nb <= 32, after fill()
     const uint32_t v = peek(nb);
     drop(nb);
     return v;
   }
   // bits consumed went past the payload: the zero bits fill() supplied were used
-  FI_PNG_HD bool over() const { return (uint64_t)pos * 8u - (uint64_t)cnt > (uint64_t)n * 8u; }
-  FI_PNG_HD uint32_t byte_pos() const { return pos - (uint32_t)(cnt >> 3); }  // once byte aligned
+  FI_ENC_HD bool over() const { return (uint64_t)pos * 8u - (uint64_t)cnt > (uint64_t)n * 8u; }
+  FI_ENC_HD uint32_t byte_pos() const { return pos - (uint32_t)(cnt >> 3); }  // once byte aligned
 };
 
 // Canonical codes of len[0..n-1] (<= 15 bits): count[l], sym[] in canonical
 // order, and the primary table over the low primbits bits.  Returns 0, 1 =
 // over-subscribed, 2 = incomplete (the tables are built all the same); *maxlen
 // = the longest length.  Lane 0 assigns the codes, the lanes fill the table.
-FI_PNG_HD int png_dec_build(const uint8_t *len, int n, uint16_t *count, uint16_t *sym, uint16_t *prim, int primbits,
+FI_ENC_HD int png_dec_build(const uint8_t *len, int n, uint16_t *count, uint16_t *sym, uint16_t *prim, int primbits,
                             uint16_t *code, int *maxlen, int lane, int nlanes) {
   FI_PNG_SYNC();  // the lengths are written, the previous tables are no longer read
   for (int i = lane; i < (1 << primbits); i += nlanes) prim[i] = 0;
@@ -216,7 +216,7 @@ FI_PNG_HD int png_dec_build(const uint8_t *len, int n, uint16_t *count, uint16_t
 // where it is 0 the code is longer: the canonical walk bit by bit (as
 // jpeg_decode_sym); -1 = a code outside the set
 template <class In>
-FI_PNG_HD int png_dec_sym(PngBits<In> &b, uint32_t e, const uint16_t *count, const uint16_t *sym) {
+FI_ENC_HD int png_dec_sym(PngBits<In> &b, uint32_t e, const uint16_t *count, const uint16_t *sym) {
   if (e) {
     b.drop((int)(e >> 9));
     return (int)(e & 511u);
@@ -242,7 +242,7 @@ FI_PNG_HD int png_dec_sym(PngBits<In> &b, uint32_t e, const uint16_t *count, con
 // where it is 0 the code has more than kPngPrimBits bits and the walk goes on
 // from W, one bit per length; -1 = a code outside the set
 template <class In>
-FI_PNG_HD int png_dec_sym_w(PngBits<In> &b, uint32_t e, const PngWalk &W, const uint16_t *sym) {
+FI_ENC_HD int png_dec_sym_w(PngBits<In> &b, uint32_t e, const PngWalk &W, const uint16_t *sym) {
   if (e) {
     b.drop((int)(e >> 9));
     return (int)(e & 511u);
@@ -269,7 +269,7 @@ FI_PNG_HD int png_dec_sym_w(PngBits<In> &b, uint32_t e, const PngWalk &W, const 
 // ring[from, to) -> out: whole dwords while `to` allows (from and out are dword
 // aligned), single bytes for the rest when `all`; returns the new `from`.
 // Every store stays below cap.
-FI_PNG_HD uint32_t png_dec_flush(const uint8_t *ring, uint8_t *out, uint32_t cap, uint32_t from, uint32_t to, bool all,
+FI_ENC_HD uint32_t png_dec_flush(const uint8_t *ring, uint8_t *out, uint32_t cap, uint32_t from, uint32_t to, bool all,
                                  int lane, int nlanes) {
   FI_PNG_SYNC();
   const uint32_t nw = (to - from) >> 2;
@@ -294,7 +294,7 @@ FI_PNG_HD uint32_t png_dec_flush(const uint8_t *ring, uint8_t *out, uint32_t cap
 // Adler-32.  Terminates on any bytes: every iteration consumes input bits or
 // emits output, and bits behind the payload are zeros that end the image.
 template <class In, class Look>
-FI_PNG_HD int png_inflate(In in, Look look, const uint8_t *raw, uint32_t n, uint8_t *ring, PngDecTabs *T, uint8_t *out,
+FI_ENC_HD int png_inflate(In in, Look look, const uint8_t *raw, uint32_t n, uint8_t *ring, PngDecTabs *T, uint8_t *out,
                           uint32_t cap, uint32_t expect, uint32_t *trailer, int lane, int nlanes) {
   constexpr uint8_t clord[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
   PngBits<In> b{in, n, 2u, 0ull, 0};  // behind CMF / FLG (fi_png_info checked them)
@@ -446,7 +446,7 @@ FI_PNG_HD int png_inflate(In in, Look look, const uint8_t *raw, uint32_t n, uint
       } else if (s == 256) {
         break;
       } else {
-        const int le = png_len_extra(s);
+        const int le = s < 265 || s == 285 ? 0 : (s - 261) >> 2;
         const int ln = s == 285 ? 258 : s < 265 ? s - 254 : 3 + ((4 + ((s - 261) & 3)) << le) + (int)b.take(le);
         b.fill();
         const int ds = png_dec_sym_w(b, look.dprim(b.peek(kPngPrimBits)), look.dw, T->dsym);
@@ -454,7 +454,7 @@ FI_PNG_HD int png_inflate(In in, Look look, const uint8_t *raw, uint32_t n, uint
           err = b.over() ? kPngErrInput : kPngErrSymbol;
           break;
         }
-        const int de = png_dist_extra(ds);
+        const int de = enc_prefix_extra(ds);
         const uint32_t dist = ds < 4 ? (uint32_t)ds + 1u : 1u + ((2u + ((uint32_t)ds & 1u)) << de) + b.take(de);
         if (b.over()) {
           err = kPngErrInput;
@@ -496,7 +496,7 @@ FI_PNG_HD int png_inflate(In in, Look look, const uint8_t *raw, uint32_t n, uint
 }
 
 // Adler-32 of d[0..n): partial sums per segment, combined (png_adler_append)
-FI_PNG_HD uint32_t png_dec_adler(const uint8_t *d, uint32_t n, uint32_t seg) {
+FI_ENC_HD uint32_t png_dec_adler(const uint8_t *d, uint32_t n, uint32_t seg) {
   uint32_t a = 1, b = 0;
   for (uint32_t s0 = 0; s0 < n; s0 += seg) {
     const uint32_t m = n - s0 < seg ? n - s0 : seg;
@@ -511,13 +511,13 @@ FI_PNG_HD uint32_t png_dec_adler(const uint8_t *d, uint32_t n, uint32_t seg) {
 }
 
 // ---- filters ---------------------------------------------------------------------------
-FI_PNG_HD int png_dec_paeth(int a, int b, int c) {  // the order a, then b, then c
+FI_ENC_HD int png_dec_paeth(int a, int b, int c) {  // the order a, then b, then c
   const int p = a + b - c;
   const int pa = p > a ? p - a : a - p, pb = p > b ? p - b : b - p, pc = p > c ? p - c : c - p;
   return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 // one reconstructed byte: x = the filtered byte, a / b / c = left, above, above left
-FI_PNG_HD int png_dec_recon(int ft, int x, int a, int b, int c) {
+FI_ENC_HD int png_dec_recon(int ft, int x, int a, int b, int c) {
   const int p = ft == 0 ? 0 : ft == 1 ? a : ft == 2 ? b : ft == 3 ? (a + b) >> 1 : png_dec_paeth(a, b, c);
   return (x + p) & 255;
 }

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "fi_enc_batch.h"
+#include "fi_enc_dev.h"
 #include "fi_enc_pack.h"
 #include "fi_internal.h"
 #include "fi_png_enc.h"
@@ -68,20 +69,6 @@ constexpr int kPngPayloadMax = 2 + kPngBand + 5 + 4;                  // zlib he
 constexpr int kPngSlotBytes = (kPngHdrBytes + 12 + kPngPayloadMax + 12 + 15) & ~15;  // + IHDR part, chunk frame, IEND
 constexpr int kPngEmitWords = (kPngPayloadMax + 3) / 4 + 8;
 
-__device__ __forceinline__ int png_scan64(int v) {  // inclusive prefix sum over the wave
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t png_sum64(uint32_t v) {  // sum over the wave, in every lane
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 __device__ __forceinline__ int png_cost(int v) {  // v = a filtered byte
   v &= 255;
   return v < 128 ? v : 256 - v;
@@ -96,15 +83,7 @@ __global__ __launch_bounds__(256) void k_png_filter(const PngDesc *__restrict__ 
                                                     uint8_t *__restrict__ stream) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < nrows; r += (int64_t)gridDim.x * 4) {
-    int lo = 0, hi = nimg;  // image of row r
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (descs[mid].row0 <= r)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    const PngDesc &D = descs[lo];
+    const PngDesc &D = descs[enc_find_image(descs, nimg, r, &PngDesc::row0)];
     const int y = (int)(r - D.row0), n = D.rowbytes, bpp = D.C;
     const uint8_t *cur = D.src + (int64_t)y * D.stride;
     const uint8_t *prev = cur - D.stride;  // read for y > 0 only
@@ -120,11 +99,11 @@ __global__ __launch_bounds__(256) void k_png_filter(const PngDesc *__restrict__ 
         c3 += png_cost(x - ((a + b) >> 1));
         c4 += png_cost(x - png_paeth(a, b, c));
       }
-      c0 = png_sum64(c0);
-      c1 = png_sum64(c1);
-      c2 = png_sum64(c2);
-      c3 = png_sum64(c3);
-      c4 = png_sum64(c4);
+      c0 = enc_sum64(c0);
+      c1 = enc_sum64(c1);
+      c2 = enc_sum64(c2);
+      c3 = enc_sum64(c3);
+      c4 = enc_sum64(c4);
       ft = 0;
       uint32_t best = c0;
       if (c1 < best) best = c1, ft = 1;
@@ -184,7 +163,7 @@ __global__ __launch_bounds__(64) void k_png_lz(const PngDesc *__restrict__ descs
   if (lane < 4) dataw[kPngBand / 4 + lane] = 0;
   for (int i = lane; i < (1 << kPngHashBits) / 2; i += 64) reinterpret_cast<uint32_t *>(tab)[i] = 0xFFFFFFFFu;
   __syncthreads();
-  for (int i = lane; i < 256; i += 64) lcost[i] = (uint8_t)png_literal_cost(hist[kPngHist + i], (uint32_t)n);
+  for (int i = lane; i < 256; i += 64) lcost[i] = (uint8_t)enc_literal_cost(hist[kPngHist + i], (uint32_t)n);
   __syncthreads();
   uint32_t *out = syms + off;
   int pos = 0, nsym = 0;  // wave-uniform: the parse position, symbols written
@@ -225,7 +204,7 @@ __global__ __launch_bounds__(64) void k_png_lz(const PngDesc *__restrict__ descs
         bool pays = true;
         if (l <= 12) {
           int eb, ev, lit = 0;
-          (void)png_dist_sym(p - cand, &eb, &ev);
+          (void)enc_prefix_sym(p - cand, &eb, &ev);
           for (int k = 0; k < l; k++) lit += lcost[bytes[p + k]];
           pays = 16 * (12 + eb) < lit;
         }
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(64) void k_png_lz(const PngDesc *__restrict__ descs
         out[at] = 0x80000000u | ((uint32_t)(mdist - 1) << 8) | (uint32_t)(mlen - 3);
         int eb, ev;
         atomicAdd(&hist[png_len_sym(mlen, &eb, &ev)], 1u);
-        atomicAdd(&hist[kPngLL + png_dist_sym(mdist, &eb, &ev)], 1u);
+        atomicAdd(&hist[kPngLL + enc_prefix_sym(mdist, &eb, &ev)], 1u);
       } else {
         const uint32_t b = bytes[p];
         out[at] = b;
@@ -260,7 +239,7 @@ __global__ __launch_bounds__(64) void k_png_lz(const PngDesc *__restrict__ descs
   }
   __syncthreads();
   for (int i = lane; i < kPngHist2; i += 64) hists[(int64_t)band * kPngHist2 + i] = hist[i];
-  const uint32_t ta = png_sum64((uint32_t)(sa % 65521u)), tb = png_sum64((uint32_t)(sb % 65521u));
+  const uint32_t ta = enc_sum64((uint32_t)(sa % 65521u)), tb = enc_sum64((uint32_t)(sb % 65521u));
   if (lane == 0) {
     nsyms[band] = nsym;
     adler[2 * band] = ta % 65521u;
@@ -302,18 +281,9 @@ __global__ __launch_bounds__(64) void k_png_codes(const PngDesc *__restrict__ de
   for (int i = lane; i < (int)(sizeof(PngBandCode) / 4); i += 64) d[i] = s[i];
 }
 
-// ORs the low nb (<= 48) bits of v into the LSB-first bit buffer at bit `bit`;
-// false (nothing written) where they would leave the buffer
+// k_png_emit's bit buffer (enc_or_bits)
 __device__ __forceinline__ bool png_put(uint32_t *buf, int bit, uint64_t v, int nb) {
-  const int w = bit >> 5, s = bit & 31;
-  if (!nb) return true;
-  if (w + 2 >= kPngEmitWords) return false;
-  const uint32_t lo = (uint32_t)v << s;
-  const uint64_t rest = v >> (32 - s);  // (s = 0: the bits from 32 up)
-  if (lo) atomicOr(&buf[w], lo);
-  if ((uint32_t)rest) atomicOr(&buf[w + 1], (uint32_t)rest);
-  if ((uint32_t)(rest >> 32)) atomicOr(&buf[w + 2], (uint32_t)(rest >> 32));
-  return true;
+  return enc_or_bits(buf, kPngEmitWords, bit, v, nb);
 }
 
 __global__ __launch_bounds__(256) void k_png_emit(const PngDesc *__restrict__ descs,
@@ -387,7 +357,7 @@ __global__ __launch_bounds__(256) void k_png_emit(const PngDesc *__restrict__ de
           nb = (int)(e >> 16);
           val |= (uint64_t)ev << nb;
           nb += eb;
-          const int ds = png_dist_sym((int)((s >> 8) & 0x7FFFu) + 1, &eb, &ev);
+          const int ds = enc_prefix_sym((int)((s >> 8) & 0x7FFFu) + 1, &eb, &ev);
           e = dtab[ds];
           val |= (uint64_t)(e & 0xFFFFu) << nb;
           nb += (int)(e >> 16);
@@ -399,16 +369,9 @@ __global__ __launch_bounds__(256) void k_png_emit(const PngDesc *__restrict__ de
           nb = (int)(e >> 16);
         }
       }
-      const int incl = png_scan64(nb);
-      if (lane == 63) wsum[wave] = incl;
-      __syncthreads();
-      int before = 0, total = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        if (k < wave) before += wsum[k];
-        total += wsum[k];
-      }
-      ok &= png_put(buf, bit + before + incl - nb, val, nb);
+      int total;
+      const int before = enc_offset256(nb, wsum, &total);
+      ok &= png_put(buf, bit + before, val, nb);
       bit += total;
       __syncthreads();
     }

@@ -19,7 +19,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "fi_png_enc.h"
+#include "fi_enc_code.h"
 
 // (fi_webp_enc.hip defines FI_WEBP_DEVICE behind hip_runtime.h: only there do the functions run on the device)
 #if defined(FI_WEBP_DEVICE) && defined(__HIP_DEVICE_COMPILE__)
@@ -79,11 +79,11 @@ int webp_enc_bound(int w, int h, int channels, size_t *bytes);
 int webp_encode_host(const uint8_t *src, int w, int h, int channels, int64_t stride, int predictor, uint8_t *out,
                      size_t out_cap, size_t *out_len);
 
-FI_PNG_HD int webp_min(int a, int b) { return a < b ? a : b; }
+FI_ENC_HD int webp_min(int a, int b) { return a < b ? a : b; }
 
 // ---- pixels -------------------------------------------------------------------
 // (A, R, G, B) of pixel (x, y): gray replicates, alpha 255 where the source has none; sg: subtract green
-FI_PNG_HD uint32_t webp_px(const WebpImg &I, int x, int y, bool sg) {
+FI_ENC_HD uint32_t webp_px(const WebpImg &I, int x, int y, bool sg) {
   const uint8_t *p = I.src + (int64_t)y * I.stride + (int64_t)x * I.C;
   uint32_t a = 255, r, g, b;
   if (I.C <= 2) {
@@ -101,16 +101,16 @@ FI_PNG_HD uint32_t webp_px(const WebpImg &I, int x, int y, bool sg) {
   }
   return (a << 24) | (r << 16) | (g << 8) | b;
 }
-FI_PNG_HD uint32_t webp_avg2(uint32_t a, uint32_t b) { return (((a ^ b) & 0xFEFEFEFEu) >> 1) + (a & b); }
-FI_PNG_HD uint32_t webp_sub(uint32_t a, uint32_t b) {  // per channel mod 256
+FI_ENC_HD uint32_t webp_avg2(uint32_t a, uint32_t b) { return (((a ^ b) & 0xFEFEFEFEu) >> 1) + (a & b); }
+FI_ENC_HD uint32_t webp_sub(uint32_t a, uint32_t b) {  // per channel mod 256
   const uint32_t ag = 0x00FF00FFu + (a & 0xFF00FF00u) - (b & 0xFF00FF00u);
   const uint32_t rb = 0xFF00FF00u + (a & 0x00FF00FFu) - (b & 0x00FF00FFu);
   return (ag & 0xFF00FF00u) | (rb & 0x00FF00FFu);
 }
-FI_PNG_HD int webp_clip(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
-FI_PNG_HD int webp_abs(int v) { return v < 0 ? -v : v; }
+FI_ENC_HD int webp_clip(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+FI_ENC_HD int webp_abs(int v) { return v < 0 ? -v : v; }
 // sum over the four residual bytes of min(x, 256 - x)
-FI_PNG_HD uint32_t webp_cost4(uint32_t v) {
+FI_ENC_HD uint32_t webp_cost4(uint32_t v) {
   uint32_t c = 0;
   for (int s = 0; s < 32; s += 8) {
     const uint32_t x = (v >> s) & 255u;
@@ -118,7 +118,7 @@ FI_PNG_HD uint32_t webp_cost4(uint32_t v) {
   }
   return c;
 }
-FI_PNG_HD uint32_t webp_predict(int mode, uint32_t L, uint32_t T, uint32_t TL, uint32_t TR) {
+FI_ENC_HD uint32_t webp_predict(int mode, uint32_t L, uint32_t T, uint32_t TL, uint32_t TR) {
   switch (mode) {
     case 0: return 0xFF000000u;
     case 1: return L;
@@ -158,7 +158,7 @@ FI_PNG_HD uint32_t webp_predict(int mode, uint32_t L, uint32_t T, uint32_t TL, u
   }
 }
 // the prediction of pixel (x, y) under `mode`, borders included
-FI_PNG_HD uint32_t webp_pred_at(const WebpImg &I, int mode, int x, int y) {
+FI_ENC_HD uint32_t webp_pred_at(const WebpImg &I, int mode, int x, int y) {
   if (y == 0) return x == 0 ? 0xFF000000u : webp_px(I, x - 1, 0, true);
   if (x == 0) return webp_px(I, 0, y - 1, true);
   const uint32_t L = webp_px(I, x - 1, y, true), T = webp_px(I, x, y - 1, true), TL = webp_px(I, x - 1, y - 1, true);
@@ -170,7 +170,7 @@ FI_PNG_HD uint32_t webp_pred_at(const WebpImg &I, int mode, int x, int y) {
 // min(x, 256 - x) over the block's residual bytes, ties to the lower mode; the
 // border pixels, whose prediction no mode changes, do not count), the mode
 // image entry and the block's residuals.  cost: 16 words all lanes share.
-FI_PNG_HD void webp_pred_block(const WebpImg &I, int blk, int lane, int nlanes, uint32_t *cost, uint32_t *resid,
+FI_ENC_HD void webp_pred_block(const WebpImg &I, int blk, int lane, int nlanes, uint32_t *cost, uint32_t *resid,
                                uint8_t *modes) {
   const int bx = blk % I.bw, by = blk / I.bw, x0 = bx << kWebpBlockBits, y0 = by << kWebpBlockBits;
   const int bwid = webp_min(16, I.W - x0), bhei = webp_min(16, I.H - y0);
@@ -203,32 +203,17 @@ FI_PNG_HD void webp_pred_block(const WebpImg &I, int blk, int lane, int nlanes, 
   if (lane == 0) modes[blk] = (uint8_t)mode;
 }
 
-// ---- backward references -------------------------------------------------------
-// a length or a distance code v >= 1 -> its prefix symbol, extra bits and their value
-FI_PNG_HD int webp_prefix(int v, int *ebits, int *eval) {
-  if (v <= 4) {
-    *ebits = 0;
-    *eval = 0;
-    return v - 1;
-  }
-  const uint32_t u = (uint32_t)v - 1;
-  const int hb = png_ilog2(u);
-  *ebits = hb - 1;
-  *eval = (int)(u & ((1u << (hb - 1)) - 1u));
-  return 2 * hb + (int)((u >> (hb - 1)) & 1u);
-}
-FI_PNG_HD int webp_prefix_extra(int sym) { return sym < 4 ? 0 : (sym >> 1) - 1; }
-
+// ---- backward references (lengths and distance codes: enc_prefix_sym) ------------
 struct WebpLzWork {  // a band's working set (LDS on the device)
   uint32_t px[kWebpBand];
   uint32_t tab[1 << kWebpHashBits];  // position + 1 of the last two-pixel prefix with this hash; 0: none
   uint32_t hist[kWebpHist];
   uint32_t cnt[4 * 256];  // byte counts per channel: A, R, G, B
-  uint8_t lcost[4 * 256];  // what a literal byte costs, in 1/16 bit (png_literal_cost; 0 for a constant channel)
+  uint8_t lcost[4 * 256];  // what a literal byte costs, in 1/16 bit (enc_literal_cost; 0 for a constant channel)
   int32_t gcand[64], ghash[64], glen[64], gdist[64];  // the current group of 64 positions
 };
 
-FI_PNG_HD int webp_match_len(const uint32_t *px, int p, int cand, int maxl) {
+FI_ENC_HD int webp_match_len(const uint32_t *px, int p, int cand, int maxl) {
   int l = 0;
   while (l < maxl && px[p + l] == px[cand + l]) l++;
   return l;
@@ -240,7 +225,7 @@ FI_PNG_HD int webp_match_len(const uint32_t *px, int p, int cand, int maxl) {
 // The parse is greedy: take the match at the position, advance by its length.
 // A match of up to 8 pixels is taken only where it costs less than its literals
 // would by the band's byte counts.
-FI_PNG_HD void webp_lz_band(const uint32_t *src, int n, int lane, int nlanes, WebpLzWork *S, uint32_t *tok,
+FI_ENC_HD void webp_lz_band(const uint32_t *src, int n, int lane, int nlanes, WebpLzWork *S, uint32_t *tok,
                             int32_t *ntok, uint32_t *bandhist, uint32_t *imghist) {
   for (int i = lane; i < kWebpHist; i += nlanes) S->hist[i] = 0;
   for (int i = lane; i < 4 * 256; i += nlanes) S->cnt[i] = 0;
@@ -256,7 +241,7 @@ FI_PNG_HD void webp_lz_band(const uint32_t *src, int n, int lane, int nlanes, We
   }
   FI_WEBP_SYNC();
   for (int i = lane; i < 4 * 256; i += nlanes)
-    S->lcost[i] = S->cnt[i] == (uint32_t)n ? 0 : (uint8_t)png_literal_cost(S->cnt[i], (uint32_t)n);
+    S->lcost[i] = S->cnt[i] == (uint32_t)n ? 0 : (uint8_t)enc_literal_cost(S->cnt[i], (uint32_t)n);
   FI_WEBP_SYNC();
   int pos = 0, nt = 0;  // the same in every lane: the parse position, tokens written
   for (int p0 = 0; p0 < n; p0 += 64) {
@@ -293,8 +278,8 @@ FI_PNG_HD void webp_lz_band(const uint32_t *src, int n, int lane, int nlanes, We
           bool pays = true;
           if (l <= 8) {
             int eb, ev, el, lit = 0;
-            (void)webp_prefix(d + 120, &eb, &ev);
-            (void)webp_prefix(l, &el, &ev);
+            (void)enc_prefix_sym(d + 120, &eb, &ev);
+            (void)enc_prefix_sym(l, &el, &ev);
             for (int j = 0; j < l; j++) {
               const uint32_t v = S->px[p + j];
               lit += S->lcost[v >> 24] + S->lcost[256 + ((v >> 16) & 255u)] + S->lcost[512 + ((v >> 8) & 255u)] +
@@ -326,8 +311,8 @@ FI_PNG_HD void webp_lz_band(const uint32_t *src, int n, int lane, int nlanes, We
       if (l) {
         tok[at] = 0x80000000u | ((uint32_t)(S->gdist[k] - 1) << 12) | (uint32_t)(l - 1);
         int eb, ev;
-        FI_WEBP_ADD(&S->hist[256 + webp_prefix(l, &eb, &ev)], 1u);
-        FI_WEBP_ADD(&S->hist[kWebpOffD + webp_prefix(S->gdist[k] + 120, &eb, &ev)], 1u);
+        FI_WEBP_ADD(&S->hist[256 + enc_prefix_sym(l, &eb, &ev)], 1u);
+        FI_WEBP_ADD(&S->hist[kWebpOffD + enc_prefix_sym(S->gdist[k] + 120, &eb, &ev)], 1u);
       } else {
         const uint32_t v = S->px[p0 + k];
         tok[at] = (uint32_t)(p0 + k);
@@ -350,28 +335,10 @@ FI_PNG_HD void webp_lz_band(const uint32_t *src, int n, int lane, int nlanes, We
 }
 
 // ---- bits, codes, header ---------------------------------------------------------
-struct WebpBits {  // LSB-first writer into zeroed words; out == nullptr: only counts
-  uint32_t *out;
-  int64_t pos, cap;  // bits
-  int32_t over;
-};
-FI_PNG_HD void webp_put(WebpBits *b, uint32_t v, int nb) {  // nb <= 32, v below 2^nb
-  if (!nb) return;
-  if (b->out) {
-    if (b->pos + nb > b->cap) {
-      b->over = 1;
-    } else {
-      const int64_t w = b->pos >> 5;
-      const int s = (int)(b->pos & 31);
-      b->out[w] |= v << s;
-      if (s + nb > 32) b->out[w + 1] |= v >> (32 - s);
-    }
-  }
-  b->pos += nb;
-}
+using WebpBits = EncBits;  // the payload's bit writer (fi_enc_code.h)
 
 struct WebpCodeWork {  // scratch of webp_write_code
-  PngHuffWork huff;
+  EncHuffWork huff;
   uint32_t freq[19];
   uint8_t lens[kWebpG];
   uint8_t cl_len[19];
@@ -384,7 +351,7 @@ struct WebpCodeWork {  // scratch of webp_write_code
 // code, and the code as the stream carries it.  Up to two used symbols below
 // 256: the simple form (one symbol: zero bits per occurrence); otherwise the
 // normal form, lengths limited to 15, complete.
-FI_PNG_HD void webp_write_code(const uint32_t *hist, int n, uint32_t *tab, WebpBits *bw, WebpCodeWork *ws) {
+FI_ENC_HD void webp_write_code(const uint32_t *hist, int n, uint32_t *tab, WebpBits *bw, WebpCodeWork *ws) {
   constexpr uint8_t clord[19] = {17, 18, 0, 1, 2, 3, 4, 5, 16, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15};
   int used = 0, s0 = 0, s1 = 0;
   for (int s = 0; s < n; s++) {
@@ -397,79 +364,33 @@ FI_PNG_HD void webp_write_code(const uint32_t *hist, int n, uint32_t *tab, WebpB
   }
   if (used == 0) used = 1;  // (symbol 0, never read)
   if (used <= 2 && (used == 1 ? s0 : s1) < 256) {
-    webp_put(bw, 1, 1);
-    webp_put(bw, (uint32_t)(used - 1), 1);
+    enc_put(bw, 1, 1);
+    enc_put(bw, (uint32_t)(used - 1), 1);
     if (s0 < 2) {
-      webp_put(bw, 0, 1);
-      webp_put(bw, (uint32_t)s0, 1);
+      enc_put(bw, 0, 1);
+      enc_put(bw, (uint32_t)s0, 1);
     } else {
-      webp_put(bw, 1, 1);
-      webp_put(bw, (uint32_t)s0, 8);
+      enc_put(bw, 1, 1);
+      enc_put(bw, (uint32_t)s0, 8);
     }
     if (used == 2) {
-      webp_put(bw, (uint32_t)s1, 8);
+      enc_put(bw, (uint32_t)s1, 8);
       tab[s0] = (1u << 16) | 0u;
       tab[s1] = (1u << 16) | 1u;
     }
     return;
   }
-  png_huff_lengths(hist, n, 15, ws->lens, &ws->huff);
-  png_huff_codes(ws->lens, n, 15, tab, ws->codes_work);
+  enc_huff_lengths(hist, n, 15, ws->lens, &ws->huff);
+  enc_huff_codes(ws->lens, n, 15, tab, ws->codes_work);
   if (used == 1) tab[s0] = 0;  // a decoder reads no bits for the only symbol
-  // the lengths run-length coded: 16 repeats the previous non-zero length, 17 / 18 are runs of zeros
-  int nr = 0;
-  for (int i = 0; i < 19; i++) ws->freq[i] = 0;
-  for (int i = 0; i < n;) {
-    const int v = ws->lens[i];
-    int run = 1;
-    while (i + run < n && ws->lens[i + run] == v) run++;
-    i += run;
-    if (v == 0) {
-      while (run >= 11) {
-        const int r = run < 138 ? run : 138;
-        ws->rle[nr++] = (uint16_t)(18 | ((r - 11) << 8));
-        ws->freq[18]++;
-        run -= r;
-      }
-      if (run >= 3) {
-        ws->rle[nr++] = (uint16_t)(17 | ((run - 3) << 8));
-        ws->freq[17]++;
-        run = 0;
-      }
-    } else {
-      ws->rle[nr++] = (uint16_t)v;
-      ws->freq[v]++;
-      run--;
-      while (run >= 3) {
-        const int r = run < 6 ? run : 6;
-        ws->rle[nr++] = (uint16_t)(16 | ((r - 3) << 8));
-        ws->freq[16]++;
-        run -= r;
-      }
-    }
-    for (; run > 0; run--) {
-      ws->rle[nr++] = (uint16_t)v;
-      ws->freq[v]++;
-    }
-  }
-  int clused = 0;
-  for (int i = 0; i < 19; i++) clused += ws->freq[i] != 0;
-  if (clused < 2) ws->freq[ws->freq[0] ? 1 : 0] = 1;  // never a one-symbol code-length code
-  png_huff_lengths(ws->freq, 19, 7, ws->cl_len, &ws->huff);
-  png_huff_codes(ws->cl_len, 19, 7, ws->cl_tab, ws->codes_work);
-  int ncl = 19;
-  while (ncl > 4 && !ws->cl_len[clord[ncl - 1]]) ncl--;
-  webp_put(bw, 0, 1);
-  webp_put(bw, (uint32_t)(ncl - 4), 4);
-  for (int i = 0; i < ncl; i++) webp_put(bw, ws->cl_len[clord[i]], 3);
-  webp_put(bw, 0, 1);  // every symbol's length follows
-  for (int i = 0; i < nr; i++) {
-    const int s = ws->rle[i] & 255, ex = ws->rle[i] >> 8;
-    webp_put(bw, ws->cl_tab[s] & 0xFFFFu, (int)(ws->cl_tab[s] >> 16));
-    if (s == 16) webp_put(bw, (uint32_t)ex, 2);
-    if (s == 17) webp_put(bw, (uint32_t)ex, 3);
-    if (s == 18) webp_put(bw, (uint32_t)ex, 7);
-  }
+  // the lengths run-length coded, in a code of their own
+  const int nr = enc_rle_lengths(ws->lens, n, ws->rle, ws->freq);
+  const int ncl = enc_cl_code(ws->freq, clord, ws->cl_len, ws->cl_tab, &ws->huff, ws->codes_work);
+  enc_put(bw, 0, 1);
+  enc_put(bw, (uint32_t)(ncl - 4), 4);
+  for (int i = 0; i < ncl; i++) enc_put(bw, ws->cl_len[clord[i]], 3);
+  enc_put(bw, 0, 1);  // every symbol's length follows
+  enc_put_rle(bw, ws->rle, nr, ws->cl_tab);
 }
 
 struct WebpBuildWork {  // scratch of webp_build_image (LDS on the device)
@@ -485,21 +406,21 @@ struct WebpBuildWork {  // scratch of webp_build_image (LDS on the device)
 // Everything of the payload before the first token: the VP8L header, the
 // transforms (the mode image with them) and the five codes, whose tables go
 // to tabs[0..kWebpHist).  coded = false: the fallback form.
-FI_PNG_HD void webp_write_head(const WebpImg &I, bool coded, const uint8_t *modes, const uint32_t *imghist,
+FI_ENC_HD void webp_write_head(const WebpImg &I, bool coded, const uint8_t *modes, const uint32_t *imghist,
                                uint32_t *tabs, WebpBits *bw, WebpBuildWork *ws) {
-  webp_put(bw, 0x2F, 8);
-  webp_put(bw, (uint32_t)(I.W - 1), 14);
-  webp_put(bw, (uint32_t)(I.H - 1), 14);
-  webp_put(bw, I.C == 2 || I.C == 4 ? 1u : 0u, 1);
-  webp_put(bw, 0, 3);
+  enc_put(bw, 0x2F, 8);
+  enc_put(bw, (uint32_t)(I.W - 1), 14);
+  enc_put(bw, (uint32_t)(I.H - 1), 14);
+  enc_put(bw, I.C == 2 || I.C == 4 ? 1u : 0u, 1);
+  enc_put(bw, 0, 3);
   const uint32_t *h = imghist;
   if (coded) {
-    webp_put(bw, 1, 1);
-    webp_put(bw, 2, 2);  // subtract green
-    webp_put(bw, 1, 1);
-    webp_put(bw, 0, 2);  // predictor
-    webp_put(bw, (uint32_t)(kWebpBlockBits - 2), 3);
-    webp_put(bw, 0, 1);  // the mode image: no colour cache; the mode in green, zeros elsewhere
+    enc_put(bw, 1, 1);
+    enc_put(bw, 2, 2);  // subtract green
+    enc_put(bw, 1, 1);
+    enc_put(bw, 0, 2);  // predictor
+    enc_put(bw, (uint32_t)(kWebpBlockBits - 2), 3);
+    enc_put(bw, 0, 1);  // the mode image: no colour cache; the mode in green, zeros elsewhere
     const int64_t nblk = (int64_t)I.bw * I.bh;
     for (int s = 0; s < kWebpG; s++) ws->hist[s] = 0;
     for (int s = 0; s < 256; s++) ws->zero[s] = 0;
@@ -507,14 +428,14 @@ FI_PNG_HD void webp_write_head(const WebpImg &I, bool coded, const uint8_t *mode
     webp_write_code(ws->hist, kWebpG, ws->mtab, bw, &ws->code);
     for (int k = 0; k < 3; k++) webp_write_code(ws->zero, 256, ws->ztab, bw, &ws->code);
     webp_write_code(ws->zero, kWebpD, ws->ztab, bw, &ws->code);
-    for (int64_t i = 0; i < nblk; i++) webp_put(bw, ws->mtab[modes[i]] & 0xFFFFu, (int)(ws->mtab[modes[i]] >> 16));
-    webp_put(bw, 0, 1);  // no further transform
+    for (int64_t i = 0; i < nblk; i++) enc_put(bw, ws->mtab[modes[i]] & 0xFFFFu, (int)(ws->mtab[modes[i]] >> 16));
+    enc_put(bw, 0, 1);  // no further transform
   } else {
     if (I.C <= 2) {  // subtract green makes red and blue constant
-      webp_put(bw, 1, 1);
-      webp_put(bw, 2, 2);
+      enc_put(bw, 1, 1);
+      enc_put(bw, 2, 2);
     }
-    webp_put(bw, 0, 1);
+    enc_put(bw, 0, 1);
     for (int s = 0; s < kWebpHist; s++) ws->hist[s] = 0;
     for (int s = 0; s < 256; s++) {
       ws->hist[kWebpOffG + s] = 1;
@@ -525,8 +446,8 @@ FI_PNG_HD void webp_write_head(const WebpImg &I, bool coded, const uint8_t *mode
     if (I.C == 1 || I.C == 3) ws->hist[kWebpOffA + 255] = 1;
     h = ws->hist;
   }
-  webp_put(bw, 0, 1);  // no colour cache
-  webp_put(bw, 0, 1);  // no meta prefix image: one Huffman group
+  enc_put(bw, 0, 1);  // no colour cache
+  enc_put(bw, 0, 1);  // no meta prefix image: one Huffman group
   webp_write_code(h + kWebpOffG, kWebpG, tabs + kWebpOffG, bw, &ws->code);
   webp_write_code(h + kWebpOffR, 256, tabs + kWebpOffR, bw, &ws->code);
   webp_write_code(h + kWebpOffB, 256, tabs + kWebpOffB, bw, &ws->code);
@@ -535,18 +456,18 @@ FI_PNG_HD void webp_write_head(const WebpImg &I, bool coded, const uint8_t *mode
 }
 
 // the bits a token takes and, LSB first, their value: a literal is G, R, B, A
-FI_PNG_HD int webp_token_bits(uint32_t tok, uint32_t argb, const uint32_t *tabs, uint64_t *val) {
+FI_ENC_HD int webp_token_bits(uint32_t tok, uint32_t argb, const uint32_t *tabs, uint64_t *val) {
   uint64_t v = 0;
   int nb = 0;
   if (tok & 0x80000000u) {
     int eb, ev;
-    const int ls = webp_prefix((int)(tok & 0xFFFu) + 1, &eb, &ev);
+    const int ls = enc_prefix_sym((int)(tok & 0xFFFu) + 1, &eb, &ev);
     uint32_t e = tabs[256 + ls];
     v = e & 0xFFFFu;
     nb = (int)(e >> 16);
     v |= (uint64_t)(uint32_t)ev << nb;
     nb += eb;
-    const int ds = webp_prefix((int)((tok >> 12) & 0x1FFFu) + 1 + 120, &eb, &ev);
+    const int ds = enc_prefix_sym((int)((tok >> 12) & 0x1FFFu) + 1 + 120, &eb, &ev);
     e = tabs[kWebpOffD + ds];
     v |= (uint64_t)(e & 0xFFFFu) << nb;
     nb += (int)(e >> 16);
@@ -575,7 +496,7 @@ FI_PNG_HD int webp_token_bits(uint32_t tok, uint32_t argb, const uint32_t *tabs,
 // head is built once, straight into the slot (the fallback's head has
 // I.fb_hdr bits whatever the image holds); only where the fallback wins is it
 // wiped and the fallback's written in its place.
-FI_PNG_HD void webp_build_image(const WebpImg &I, const uint32_t *imghist, const uint8_t *modes,
+FI_ENC_HD void webp_build_image(const WebpImg &I, const uint32_t *imghist, const uint8_t *modes,
                                 const uint32_t *bandhists, int lane, int nlanes, WebpBuildWork *ws, uint32_t *tabs,
                                 int64_t *bandoff, uint32_t *slot, WebpImgOut *out, int32_t *fault) {
   uint32_t *pay = slot + kWebpRiffBytes / 4;
@@ -592,7 +513,7 @@ FI_PNG_HD void webp_build_image(const WebpImg &I, const uint32_t *imghist, const
     const uint32_t *hb = bandhists + (int64_t)b * kWebpHist;
     int64_t bits = 0;
     for (int s = 0; s < kWebpHist; s++) {
-      const int extra = s >= 256 && s < kWebpG ? webp_prefix_extra(s - 256) : s >= kWebpOffD ? webp_prefix_extra(s - kWebpOffD) : 0;
+      const int extra = s >= 256 && s < kWebpG ? enc_prefix_extra(s - 256) : s >= kWebpOffD ? enc_prefix_extra(s - kWebpOffD) : 0;
       bits += (int64_t)hb[s] * ((tabs[s] >> 16) + (uint32_t)extra);
     }
     bandoff[b] = bits;

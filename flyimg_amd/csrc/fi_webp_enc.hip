@@ -13,7 +13,7 @@
 //            pixel before; greedy parse with a cost gate; tokens -> scratch,
 //            the band's histograms -> its record and, added, the image's five;
 //   k_webp_codes  a wave per image: lane 0 builds the five codes with the
-//            length-limited builder of fi_png_enc.h and writes the RIFF and
+//            length-limited builder of fi_enc_code.h and writes the RIFF and
 //            VP8L headers, the transforms, the mode image and the codes into the
 //            image's zeroed slot; the lanes price the bands from their
 //            histograms; prefix sum -> each band's bit offset; the fallback
@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "fi_enc_batch.h"
+#include "fi_enc_dev.h"
 #include "fi_enc_pack.h"
 #include "fi_internal.h"
 #define FI_WEBP_DEVICE 1
@@ -50,15 +51,7 @@ __global__ __launch_bounds__(64) void k_webp_pred(const WebpImg *__restrict__ de
   __shared__ uint32_t cost[16];
   const int64_t blk = blockIdx.x;
   if (blk >= nblocks) return;
-  int lo = 0, hi = nimg;  // image of block blk
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (descs[mid].block0 <= blk)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  const WebpImg &I = descs[lo];
+  const WebpImg &I = descs[enc_find_image(descs, nimg, blk, &WebpImg::block0)];
   webp_pred_block(I, (int)(blk - I.block0), (int)threadIdx.x, 64, cost, resid + I.px0, modes + I.block0);
 }
 
@@ -92,16 +85,6 @@ __global__ __launch_bounds__(64) void k_webp_codes(const WebpImg *__restrict__ d
                    reinterpret_cast<uint32_t *>(slots + I.slot0), outs + img, fault);
 }
 
-__device__ __forceinline__ int webp_scan64(int v) {  // inclusive prefix sum over the wave
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(256) void k_webp_emit(const WebpImg *__restrict__ descs,
                                                    const WebpBandRef *__restrict__ bands, int nbands,
                                                    const uint32_t *__restrict__ resid, const uint32_t *__restrict__ toks,
@@ -112,7 +95,7 @@ __global__ __launch_bounds__(256) void k_webp_emit(const WebpImg *__restrict__ d
   __shared__ uint32_t tabs[kWebpHist];
   __shared__ uint32_t buf[kWebpChunkWords];
   __shared__ int wsum[4];
-  const int band = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int band = blockIdx.x, t = threadIdx.x;
   if (band >= nbands) return;
   const WebpBandRef B = bands[band];
   const WebpImg &I = descs[B.img];
@@ -148,25 +131,11 @@ __global__ __launch_bounds__(256) void k_webp_emit(const WebpImg *__restrict__ d
       }
       nb = webp_token_bits(tok, argb, tabs, &val);
     }
-    const int incl = webp_scan64(nb);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (k < wave) before += wsum[k];
-      total += wsum[k];
-    }
+    int total;
+    const int before = enc_offset256(nb, wsum, &total);
     const int64_t w0 = cur >> 5;
-    if (nb) {
-      const int lb = (int)(cur & 31) + before + incl - nb;
-      const int w = lb >> 5, s = lb & 31;
-      const uint32_t lo = (uint32_t)val << s;
-      const uint64_t rest = val >> (32 - s);  // (s = 0: the bits from 32 up)
-      if (lo) atomicOr(&buf[w], lo);
-      if ((uint32_t)rest) atomicOr(&buf[w + 1], (uint32_t)rest);
-      if ((uint32_t)(rest >> 32)) atomicOr(&buf[w + 2], (uint32_t)(rest >> 32));
-    }
+    // (no guard: a chunk is at most 31 + 256 * 60 bits, which kWebpChunkWords holds)
+    (void)enc_or_bits<false>(buf, kWebpChunkWords, (int)(cur & 31) + before, val, nb);
     __syncthreads();
     const int64_t endbit = cur + total;
     const int nfull = (int)((endbit >> 5) - w0);  // dwords complete after this chunk

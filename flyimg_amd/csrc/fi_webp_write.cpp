@@ -86,11 +86,11 @@ int webp_encode_host(const uint8_t *src, int w, int h, int channels, int64_t str
                    slot.data(), &R, &fault);
   if (fault) return FI_EDEVICE;
   // the tokens, band by band, at the bit offsets the image was priced with
-  uint32_t *pay = slot.data() + kWebpRiffBytes / 4;
+  WebpBits bw{slot.data() + kWebpRiffBytes / 4, 0, (I.slot_bytes - kWebpRiffBytes) * 8, 0};
   for (int b = 0; b < I.nbands; b++) {
     const int n = webp_min(kWebpBand, I.npix - b * kWebpBand);
     const int nt = R.fallback ? n : ntok[b];
-    int64_t bit = bandoff[b];
+    bw.pos = bandoff[b];
     for (int i = 0; i < nt; i++) {
       const uint32_t t = R.fallback ? (uint32_t)i : tok[(size_t)b * kWebpBand + i];
       uint32_t argb = 0;
@@ -99,19 +99,12 @@ int webp_encode_host(const uint8_t *src, int w, int h, int channels, int64_t str
         argb = R.fallback ? webp_px(I, (int)(p % I.W), (int)(p / I.W), I.C <= 2) : resid[(size_t)p];
       }
       uint64_t v;
-      const int nb = webp_token_bits(t, argb, tabs.data(), &v);
-      if (bit + nb > (I.slot_bytes - kWebpRiffBytes) * 8) return FI_EDEVICE;
-      for (int k = 0; k < nb; k += 32) {
-        const int m = webp_min(32, nb - k);
-        const uint32_t part = (uint32_t)(v >> k) & (m == 32 ? 0xFFFFFFFFu : (1u << m) - 1u);
-        const int64_t wd = (bit + k) >> 5;
-        const int s = (int)((bit + k) & 31);
-        pay[wd] |= part << s;
-        if (s + m > 32) pay[wd + 1] |= part >> (32 - s);
-      }
-      bit += nb;
+      const int nb = webp_token_bits(t, argb, tabs.data(), &v);  // at most 60 bits
+      enc_put(&bw, (uint32_t)v, webp_min(nb, 32));
+      if (nb > 32) enc_put(&bw, (uint32_t)(v >> 32), nb - 32);
+      if (bw.over) return FI_EDEVICE;
     }
-    if (bit != (b + 1 < I.nbands ? bandoff[b + 1] : R.total_bits)) return FI_EDEVICE;
+    if (bw.pos != (b + 1 < I.nbands ? bandoff[b + 1] : R.total_bits)) return FI_EDEVICE;
   }
   *out_len = (size_t)R.file_bytes;
   if ((size_t)R.file_bytes > out_cap) return FI_ENOMEM;

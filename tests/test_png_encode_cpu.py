@@ -2,9 +2,11 @@
 fi_png_encode_bound, and -- built stand-alone under ASan/UBSan
 (tests/native/png_write_driver.cpp, its own process, nothing preloaded) --
 the fixed chunks against Pillow's, the CRC-32 and Adler-32 combination against
-zlib, and the code builder the device runs per band (fi_png_enc.h:
-png_huff_lengths, png_huff_codes, png_build_block) on histograms chosen to
-break it, down to a whole dynamic block that zlib inflates."""
+zlib, and the code builder the device runs per band (fi_enc_code.h:
+enc_huff_lengths, enc_huff_codes; fi_png_enc.h: png_build_block) on histograms
+chosen to break it, down to a whole dynamic block that zlib inflates; then the
+rest of the layer the PNG and WebP encoders share (fi_enc_code.h) on its own:
+the run-length coder of code lengths and the bit writer."""
 import io
 import os
 import subprocess
@@ -181,22 +183,30 @@ def _check_code(freq, maxbits, line):
     return lens
 
 
-def test_code_builder_on_hard_histograms(driver):
+def _huff_cases():
+    """(maxbits, histogram): case 0 has one used symbol, 65"""
     rng = np.random.default_rng(3)
-    cases = []
     one = [0] * 286
     one[65] = 9
     two = [0] * 286
     two[0], two[256] = 1000, 1
-    cases += [(15, one), (15, two), (15, [7] * 286), (15, _fib(40) + [0] * 246), (15, [0] * 246 + _fib(40)[::-1]),
-              (7, _fib(19)), (7, [0, 5, 0, 0] + _fib(15)), (7, [1] * 19), (7, [0] * 18 + [3]),
-              (15, [1] * 285 + [32768]), (15, list(map(int, rng.integers(0, 3, 286)))),
-              (15, list(map(int, rng.integers(1, 40000, 286)))), (15, [2 ** k for k in range(30)]),
-              (15, list(map(int, rng.geometric(0.002, 30))))]
-    out = driver(["huff %d %s" % (m, " ".join(map(str, f))) for m, f in cases])
-    for (m, f), line in zip(cases, out):
+    return [(15, one), (15, two), (15, [7] * 286), (15, _fib(40) + [0] * 246), (15, [0] * 246 + _fib(40)[::-1]),
+            (7, _fib(19)), (7, [0, 5, 0, 0] + _fib(15)), (7, [1] * 19), (7, [0] * 18 + [3]),
+            (15, [1] * 285 + [32768]), (15, list(map(int, rng.integers(0, 3, 286)))),
+            (15, list(map(int, rng.integers(1, 40000, 286)))), (15, [2 ** k for k in range(30)]),
+            (15, list(map(int, rng.geometric(0.002, 30))))]
+
+
+def _huff_lines():
+    return ["huff %d %s" % (m, " ".join(map(str, f))) for m, f in _huff_cases()]
+
+
+def test_code_builder_on_hard_histograms(driver):
+    cases = _huff_cases()
+    out = driver(_huff_lines())
+    for k, ((m, f), line) in enumerate(zip(cases, out)):
         lens = _check_code(f, m, line)
-        if f is one:
+        if k == 0:
             assert lens[65] == 1
     # the limit acts: an unlimited code of 40 Fibonacci frequencies is 39 deep
     assert max(_check_code(cases[3][1], 15, out[3])) == 15
@@ -238,14 +248,18 @@ def _block_cases():
     return cases
 
 
+def _block_lines(last):
+    lines = []
+    for syms in _block_cases():
+        toks = [f"{s[0]},{s[1]}" if isinstance(s, tuple) else str(s) for s in syms]
+        lines.append(f"block {last} {len(_expand(syms))} " + " ".join(toks))
+    return lines
+
+
 @pytest.mark.parametrize("last", [1, 0])
 def test_dynamic_block_inflates(driver, last):
     cases = _block_cases()
-    lines = []
-    for syms in cases:
-        toks = [f"{s[0]},{s[1]}" if isinstance(s, tuple) else str(s) for s in syms]
-        lines.append(f"block {last} {len(_expand(syms))} " + " ".join(toks))
-    out = driver(lines)
+    out = driver(_block_lines(last))
     for k, (syms, line) in enumerate(zip(cases, out)):
         _, stored, block_bits, pos, hx = line.split()
         want = _expand(syms)
@@ -261,3 +275,100 @@ def test_dynamic_block_inflates(driver, last):
         assert z.eof and z.unused_data == b""
         assert int(stored) == (1 if dyn_bytes >= len(want) + 5 else 0), k
     assert out[4].split()[1] == "1" and out[0].split()[1] == "0"
+
+
+# ---- the layer the PNG and WebP encoders share (fi_enc_code.h) --------------------
+RLE_RANGE = {16: (3, 6), 17: (3, 10), 18: (11, 138)}
+
+
+def _rle_cases():
+    """Code-length sequences: zero runs on both sides of 3, 11 and 138 (and of
+    two symbols 18), non-zero runs on both sides of 3 and of every count of
+    symbols 16, a run directly behind a run of the other kind, and the longest
+    sequences the formats send (deflate's 286 + 30, VP8L's 280)."""
+    rng = np.random.default_rng(17)
+    cases = [[5] + [0] * z + [7] for z in (1, 2, 3, 10, 11, 138, 139, 140, 149, 276)]
+    cases += [[0] * z for z in (1, 2, 3, 10, 11, 138, 139, 140, 149, 276)]
+    cases += [[0] + [9] * r + [0] for r in (1, 2, 3, 4, 6, 7, 8, 9, 13)]
+    cases += [[9] * r for r in (1, 2, 3, 4, 6, 7, 8, 9, 13)]
+    cases += [[0] * 12 + [4] * 5, [4] * 5 + [0] * 12, [0] * 3 + [1] * 4 + [0] * 11 + [2] * 8, [3] * 7 + [4] * 7]
+    cases += [[0], [15], list(map(int, rng.integers(0, 16, 286 + 30))), list(map(int, rng.integers(0, 3, 286 + 30))),
+              list(map(int, rng.integers(0, 16, 280))), [0] * 256 + [8] * 24, [8] * 280, [0] * (286 + 30)]
+    return cases
+
+
+def test_code_length_run_length_coder(driver):
+    cases = _rle_cases()
+    out = driver(["rle " + " ".join(map(str, c)) for c in cases])
+    for lens, line in zip(cases, out):
+        tag, *ent = line.split()
+        assert tag == "RLE", line
+        got, nsym = [], 0
+        for e in ent:
+            s, ex = map(int, e.split(":"))
+            nsym += 1
+            if s < 16:
+                assert ex == 0
+                got.append(s)
+                continue
+            lo, hi = RLE_RANGE[s]
+            assert lo <= lo + ex <= hi, (s, ex)
+            if s == 16:
+                assert got and got[-1] != 0, "16 repeats a length that was sent"
+                got += [got[-1]] * (lo + ex)
+            else:
+                got += [0] * (lo + ex)
+        assert got == lens, (lens, ent)
+        assert nsym <= len(lens)
+    # the runs take the symbols they are meant to: 138 zeros are one symbol 18, 139 are 18 and a plain zero
+    assert out[15].split()[1:] == ["18:127"] and out[16].split()[1:] == ["18:127", "0:0"]
+    assert out[18].split()[1:] == ["18:127", "18:0"] and out[12].split()[1:] == ["17:0"]
+
+
+def _bits_model(cap, puts):
+    """enc_put on a string of cap bits, LSB first: a write that would pass
+    the capacity sets the flag, writes nothing, and still counts."""
+    bits, pos, over, at = [0] * cap, 0, 0, []
+    for v, w in puts:
+        if w and pos + w > cap:
+            over = 1
+        else:
+            for k in range(w):
+                bits[pos + k] |= (v >> k) & 1
+        pos += w
+        at.append(pos)
+    by = bytearray(-(-cap // 8))
+    for i, b in enumerate(bits):
+        by[i >> 3] |= b << (i & 7)
+    return over, by.hex(), at
+
+
+def _bits_cases():
+    full = {0: 0, 1: 1, 31: 0x5A5A5A5A & 0x7FFFFFFF, 32: 0xDEADBEEF}
+    leads = {0: [], 1: [(1, 1)], 31: [(0x7FFFFFFF, 31)], 33: [(0x7FFFFFFF, 31), (1, 1), (1, 1)]}
+    cases = []
+    for off, lead in leads.items():  # every width at every bit offset, and a bit behind it
+        assert sum(w for _, w in lead) == off
+        for w in (0, 1, 31, 32):
+            cases.append((128, lead + [(full[w], w), (1, 1)]))
+    cases.append((64, [(0xFFFFFFFF, 32), (0x80000001, 32)]))                  # ends exactly at the capacity
+    cases.append((64, [(0xFFFFFFFF, 32), (0x7FFFFFFF, 31), (3, 2), (1, 1)]))  # one bit past it: nothing written
+    cases.append((33, [(0xFFFFFFFF, 32), (1, 1)]))
+    cases.append((33, [(3, 2), (0xFFFFFFFF, 32), (1, 1)]))                    # the refused write straddles a word
+    cases.append((0, [(1, 1)]))
+    return cases
+
+
+def test_bit_writer_matches_a_bit_string_model(driver):
+    cases = _bits_cases()
+    out = driver([f"bits {cap} " + " ".join(f"{v}:{w}" for v, w in puts) for cap, puts in cases])
+    overs = []
+    for (cap, puts), line in zip(cases, out):
+        tag, over, *rest = line.split()
+        hx = rest[0] if len(rest) == 3 else ""   # (a capacity of 0 bits prints no bytes)
+        at, atc = rest[-2], rest[-1]
+        want_over, want_hex, want_at = _bits_model(cap, puts)
+        assert tag == "BITS" and (int(over), hx) == (want_over, want_hex), (cap, puts, line)
+        assert list(map(int, at.split(","))) == want_at and atc == at, (cap, puts, line)
+        overs.append(int(over))
+    assert overs[-5:] == [0, 1, 0, 1, 1] and not any(overs[:-5])
