@@ -1,4 +1,4 @@
-// fi_internal.h -- structures shared by the host planner (fi_plan.cpp), the
+// fi_internal.h -- structures shared by the host planner (fi_plan*.cpp), the
 // runtime (fi_runtime.h and its files) and the gfx950 kernels (fi_kernels.hip).
 //
 // Data layout in HBM (see DESIGN.md "Data layout"):
@@ -155,7 +155,7 @@ struct ScDesc {
   int32_t sg_lds, sg_pad;  // its dynamic LDS
 };
 
-// smartcrop prescale planning (fi_plan.cpp plan_sc_prep): kPrepRows rows per
+// smartcrop prescale planning (fi_plan_sc.cpp plan_sc_prep): kPrepRows rows per
 // chunk; apitch = 16-B rounded aw*3 (hbuf and LDS row pitch), spitch = 16-B
 // rounded source width*3.  LDS per workgroup <= kPrepMaxLds (host-checked).
 constexpr int kPrepRows = 16;

@@ -4,7 +4,7 @@
 // fi_jpeg_api.cpp, fi_rccl.cpp, fi_api.cpp.
 //
 // One fi_ctx per process per GPU.  A batch call:
-//   1. plans every image on the host (fi_plan.cpp): ImageMagick geometry,
+//   1. plans every image on the host (fi_plan*.cpp): ImageMagick geometry,
 //      merged tap tables, Pillow prescale tables, smartcrop crop windows and
 //      importance tables -- deduplicated per geometry and cached across calls;
 //   2. packs descriptors + tables into ONE pinned blob and uploads it with

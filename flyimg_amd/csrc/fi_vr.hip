@@ -4,7 +4,7 @@
 // vertical pass: v_mfma_i32_16x16x64_i8.
 //
 // Weights rint(w 2^s) in two signed-byte limbs, every output row summing to
-// 2^s (fi_plan.cpp vr_quant; bounded against IM's f64 weights by
+// 2^s (fi_plan_mfma.cpp vr_quant; bounded against IM's f64 weights by
 // tests/native/vr_quant_bound.cpp).  k_rs_vm carries the same weights scaled
 // to 2^22 in three limbs (axis_q22), so the two kernels give the same pixels;
 // what differs is how the vertical pass walks the source rows (DESIGN.md 3.0,

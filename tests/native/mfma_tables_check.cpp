@@ -1,4 +1,4 @@
-// CPU check of the k_rs_vm / k_sc_hmfma host tables (fi_plan.cpp): the
+// CPU check of the k_rs_vm / k_sc_hmfma host tables (fi_plan_mfma.cpp, fi_plan_sc.cpp): the
 // weight matrices rebuilt from the fragment bytes through mfma_i8_k must give,
 // with the kernel's integer algebra, exactly sum(quant(w) * p) for every
 // output -- for the vertical pass over the touched-row list, the horizontal

@@ -21,6 +21,7 @@ import pytest
 
 from oracle import oracle as orc
 from tests import _adversarial as A
+from tests._planner import PLANNER_SRCS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -162,7 +163,7 @@ def vr_quant_bound_output():
                        timeout=300)
         subprocess.run([hipcc, "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
                         os.path.join(ROOT, "tests/native/vr_quant_bound.cpp"),
-                        os.path.join(ROOT, "flyimg_amd/csrc/fi_plan.cpp"), "-Xlinker", obj, "-o", exe, "-lm"],
+                        *PLANNER_SRCS, "-Xlinker", obj, "-o", exe, "-lm"],
                        check=True, capture_output=True, timeout=300)
         r = subprocess.run([exe, "adversarial"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr

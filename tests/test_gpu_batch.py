@@ -6,7 +6,7 @@ offsets derived from them -- run past 2^32, through fi_process_batch_device
 smart-crop box bit-exact on the GPU-resized pixels, applied crop == that box.
 Also the same batch on the k_rs_vm kernel (FI_VR_RS=0) is byte for byte
 k_rs_vr's (the default): k_rs_vm carries k_rs_vr's two-limb weights scaled to
-2^22 (fi_plan.cpp axis_q22)."""
+2^22 (fi_plan_mfma.cpp axis_q22)."""
 import os
 
 import numpy as np

@@ -1,7 +1,7 @@
 """k_rs_vr (the persistent block-major resample, fi_vr.hip) on every geometry
 class it takes: the path actually ran (its image counter rose by the batch),
 the output is bit-identical to k_rs_vm's (which carries k_rs_vr's two-limb
-weights scaled to 2^22, fi_plan.cpp axis_q22 -- so an image's pixels do not
+weights scaled to 2^22, fi_plan_mfma.cpp axis_q22 -- so an image's pixels do not
 depend on which kernel its batch took), and within +-1 LSB / >= 99.5 % exact (99.9 % on the BASELINE geometries) of
 the oracle (ImageProcessor.php:86 -thumbnail / -resize, IM's VerticalFilter
 then HorizontalFilter)."""

@@ -1,5 +1,5 @@
 """Host-side native checks (CPU): the exact-integer MFMA tables built by
-flyimg_amd/csrc/fi_plan.cpp reproduce sum(quant(w) * p) through the kernels'
+the host planner (tests/_planner.py PLANNER_SRCS) reproduce sum(quant(w) * p) through the kernels'
 integer algebra (tests/native/mfma_tables_check.cpp, compiled host-only)."""
 import os
 import shutil
@@ -7,6 +7,8 @@ import subprocess
 import tempfile
 
 import pytest
+
+from tests._planner import PLANNER_SRCS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -19,7 +21,7 @@ def test_mfma_tables_exact():
         exe = os.path.join(d, "mtc")
         subprocess.run([hipcc, "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
                         os.path.join(ROOT, "tests/native/mfma_tables_check.cpp"),
-                        os.path.join(ROOT, "flyimg_amd/csrc/fi_plan.cpp"), "-o", exe],
+                        *PLANNER_SRCS, "-o", exe],
                        check=True, capture_output=True, timeout=300)
         r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, r.stdout + r.stderr
@@ -27,7 +29,7 @@ def test_mfma_tables_exact():
 
 
 def test_vr_two_limb_quantisation_bound():
-    """k_rs_vr's two-limb weights (fi_plan.cpp vr_quant / quant_axis): every
+    """k_rs_vr's two-limb weights (fi_plan_mfma.cpp vr_quant / quant_axis): every
     table of the BASELINE geometries and 200 random ones is rebuilt from its
     fragment bytes, its integer algebra re-derived (row sums 2^shift, the
     constant 128 * 2^shift bias, the Q16 hi/lo split), and the worst case over
@@ -50,7 +52,7 @@ def test_vr_two_limb_quantisation_bound():
                        timeout=300)
         subprocess.run([hipcc, "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
                         os.path.join(ROOT, "tests/native/vr_quant_bound.cpp"),
-                        os.path.join(ROOT, "flyimg_amd/csrc/fi_plan.cpp"), "-Xlinker", obj, "-o", exe, "-lm"],
+                        *PLANNER_SRCS, "-Xlinker", obj, "-o", exe, "-lm"],
                        check=True, capture_output=True, timeout=300)
         r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr

@@ -9,6 +9,14 @@ descriptor field, tile order and heap offset is in those bytes, so a refactor
 of the planner that moves one of them fails here, on the CPU, before any pixel
 test runs.
 
+test_planner_tables_are_unchanged does the same one level down: it compiles
+tests/native/plan_driver.cpp with the planner's sources alone and compares the
+digest of every structure fi_plan.h's builders fill -- each scalar field and
+vector of ImPlan, the tap axes, the quantised weights, the MFMA tables of the
+three resample kernels, ScPlan with its fragment tables, the importance and
+score tables -- on tests/_planner.py plan_lines(), one digest per builder per
+input line so that a mismatch names the builder.
+
 This pins bytes, not correctness.  A change that alters the planner's output on
 purpose re-records the file (the failure message prints the new values) and
 says so in its description.
@@ -16,11 +24,16 @@ says so in its description.
 import ctypes
 import json
 import os
+import re
+import shutil
+import subprocess
+import tempfile
 
 import pytest
 
 import bench
 from flyimg_amd import _lib as L
+from tests._planner import PLANNER_SRCS, ROOT, plan_lines
 from tests.test_plan_cpu import _batch
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "plan_digests.json")
@@ -93,3 +106,45 @@ def test_planner_output_is_unchanged(vr_rs, monkeypatch):
     assert len(want) == len(got) and not diff, (
         "the planner's output changed; first difference (recorded, now): %r\nnew values:\n%s"
         % (diff[:1], json.dumps(got, indent=1)))
+
+
+# every table variant a fragment writer of the planner can take (plan_driver's
+# DONE line: name=count), and the builders (name=built/refused)
+VARIANTS = ("plan_im.gray", "plan_im.shear", "axis.outputs_not_16n", "mfma_h.frag2", "mfma_h.ks2", "mfma_h.frag2_ks2",
+            "vm_v.rstep0", "vr_v.ks2", "vr_v.rstep0", "hv_h.ks2", "hv_v.ks2", "sc.hm", "sc.hm_ks2", "sc.vq", "sc.cx",
+            "sc.cx_kv2", "sc.fz", "sc.reduce", "sc.hm_not_vq", "importance.wider_than_64", "score_btab.ks1",
+            "score_btab.ks2")
+BUILDERS = ("plan_im", "axis_v", "axis_h", "vr_quant_v", "vr_quant_h", "axis_q22_v", "axis_q22_h", "mfma_h168",
+            "mfma_h64", "mfma_h48", "mfma_h32", "vm_v", "vr_v", "hv_h", "hv_v", "plan_sc", "importance_image",
+            "importance_window", "score_btab1", "score_btab2", "score_btab3", "score_btab_image")
+
+
+def test_planner_tables_are_unchanged():
+    """Every builder's digest on every input line equals the recorded one, and
+    the inputs reach every builder and every table variant at least once."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    lines = plan_lines()
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "plan_driver")
+        subprocess.run([hipcc, "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "tests/native/plan_driver.cpp"), *PLANNER_SRCS, "-o", exe],
+                       check=True, capture_output=True, timeout=300)
+        stdin = "".join(" ".join(str(int(v)) for v in ln) + "\n" for ln in lines)
+        r = subprocess.run([exe], input=stdin, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    got = r.stdout.splitlines()
+    assert got and got[-1].startswith(f"DONE {len(lines)} images;"), got[-1:]
+    done = dict(kv.split("=") for kv in got[-1].split(";")[1].split())
+    for b in BUILDERS:
+        assert int(done[b].split("/")[0]) > 0, (b, done[b])
+    for v in VARIANTS:
+        assert int(done[v]) > 0, (v, done[v])
+    assert set(done) == set(BUILDERS) | set(VARIANTS), sorted(set(done) ^ (set(BUILDERS) | set(VARIANTS)))
+    with open(GOLDEN) as f:
+        want = json.load(f)["tables"]
+    diff = [(w, g) for w, g in zip(want, got) if w != g]
+    assert len(want) == len(got) and not diff, (
+        "the planner's tables changed; first differences (recorded, now): %r; builders that differ: %s"
+        % (diff[:3], sorted({re.split(" ", g)[1] for _, g in diff})))
